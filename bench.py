@@ -15,8 +15,14 @@ Prints ONE JSON line (rank 0).  NK_BENCH_SHAPE=256,256,256 / NK_BENCH_DTYPE=f64 
 for quick checks (the line then names that workload and is not the headline number).
 NK_BENCH_CONFIG=C2 | C3 | C4 selects another BASELINE.json config as a side measurement (C4: 4096^2
 sigmoid(cf) -> masked LOSResponse(10^4 lines) -> Gaussian, geoVI, on the fused response engine).
-NK_BENCH_SAMPLES=16 runs BASELINE configs[4]'s sample count; from 4 ranks on a short 16-sample leg is
-appended to the line as "samples16" automatically (NK_BENCH_ALSO16=0: off, =force: from 2 ranks on).
+NK_BENCH_SAMPLES=16 runs BASELINE configs[4]'s sample count.
+
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds everything else the bench
+measures: the live per-kernel HIP events of the timed steps (`roofline`, `step_hbm_GBps_rank0`) with a device-copy
+ceiling after them, the per-phase clock (`phase_seconds_per_step_rank0`) and the exchange timer of world > 1, the oracle
+CPU baseline with its in-run parity check (`cpu_baseline`; --no-cpu-baseline drops it), from 4 ranks on a short
+16-sample leg as "samples16" (NK_BENCH_ALSO16=0: off, =force: from 2 ranks on) and the NK_BENCH_API=1 leg.
+--dump-outputs DIR writes what the last timed step returned (the new latent mean and the KL energy) as DIR/*.npy.
 """
 import argparse
 import ctypes
@@ -35,7 +41,7 @@ sys.path.insert(0, ROOT)
 from nifty_amd import _lib as L  # noqa: E402
 from nifty_amd import backend as B  # noqa: E402
 from nifty_amd import minimization, parallel, random  # noqa: E402
-from nifty_amd.engine import FusedKL, FusedModel, LatentVec, draw_samples, mgvi_iteration  # noqa: E402
+from nifty_amd.engine import SMALL_KEYS, FusedKL, FusedModel, LatentVec, draw_samples, mgvi_iteration  # noqa: E402
 from nifty_amd.minimization import AbsDeltaEnergyController, NewtonCG  # noqa: E402
 
 # streams of the fused CG vector update: x, r (read + write), d, q -- plus b when the energy is re-evaluated from x.b
@@ -383,6 +389,31 @@ def api_leg(shape, dtype, lh_kind, noise_var, data, n_pairs, steps, device, engi
     return out
 
 
+DUMP_XI_FULL_BYTES = 48 << 20  # --dump-outputs: xi is written whole up to this size ...
+DUMP_XI_SAMPLE = 1 << 22       # ... else as this many entries at seeded random flat indices (16 / 32 MB in fp32 / fp64)
+DUMP_SAMPLE_SEED = 20250917
+
+
+def dump_outputs(directory, mean, energy):
+    """--dump-outputs: what the caller of the timed path (engine.mgvi_iteration) received from the last timed step -- the new
+    latent mean, keyed like LatentVec.to_dict(), and the sampled KL energy -- as DIR/<name>.npy in the field dtype (xi) or
+    fp64.  An xi larger than DUMP_XI_FULL_BYTES is written as `mean_xi_sample`: its entries at DUMP_XI_SAMPLE sorted flat
+    indices drawn from a fixed seed, the same for every run of the same grid.  Well under 64 MB in all."""
+    os.makedirs(directory, exist_ok=True)
+    small = mean.small.cpu().numpy().astype(np.float64)
+    arrays = {f"mean_{k}": np.array(small[i]) for i, k in enumerate(SMALL_KEYS)}
+    arrays["mean_spectrum"] = small[len(SMALL_KEYS):].reshape(2, -1).copy()
+    flat = mean.xi.reshape(-1)
+    if flat.numel() * flat.element_size() <= DUMP_XI_FULL_BYTES:
+        arrays["mean_xi"] = mean.xi.cpu().numpy()
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, flat.numel(), DUMP_XI_SAMPLE))
+        arrays["mean_xi_sample"] = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy()
+    arrays["kl_energy"] = np.array(float(energy), dtype=np.float64)
+    for name, arr in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), arr)
+
+
 RNG_LABEL = {"numpy": "the reference's numpy PCG64 + ziggurat streams (seed 42, one SeedSequence per sample), computed on the "
                       "device from the host generators' states (nk_pcg64_normal)",
              "device": "torch device generator (NK_BENCH_RNG=device)"}
@@ -393,7 +424,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the oracle CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements: per-kernel roofline, copy ceiling, phase and exchange clocks, CPU "
+                         "baseline with parity check, 16-sample leg, NK_BENCH_API leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -487,17 +523,18 @@ def main():
     rng_draws = torch.Generator(device=device).manual_seed(1234 + rank) if rng_mode == "device" else None
 
     phases = {}
-    phase_timing = os.environ.get("NK_BENCH_PHASES", "1" if (comm is not None or N >= (1 << 27)) else "0") == "1"
+    phase_timing = os.environ.get("NK_BENCH_PHASES",
+                                  "1" if args.full and (comm is not None or N >= (1 << 27)) else "0") == "1"
 
     def step(mean, pairs=n_pairs):
         ic = lambda: AbsDeltaEnergyController(0.05, iteration_limit=20)  # noqa: E731
         mini = NewtonCG(AbsDeltaEnergyController(0.5, convergence_level=2, iteration_limit=3), max_cg_iterations=20)
         # C4: geoVI, the non-linear sample fit of demos/cl/getting_started_3.py:125-127
         geo = NewtonCG(AbsDeltaEnergyController(0.5, iteration_limit=5, convergence_level=2)) if cfg == "C4" else None
-        # the timed code is the engine's own entry point; with NK_BENCH_PHASES (default on for world > 1 and for grids >= 2^27
-        # points, where three extra synchronisations per step are noise) a hook at its phase boundaries synchronises the
-        # device and reads the clock: sampling has no exchange, the KL construction one all-reduce, the Newton-CG one exchange
-        # per CG iteration
+        # the timed code is the engine's own entry point; with NK_BENCH_PHASES (default with --full on for world > 1 and for
+        # grids >= 2^27 points, where three extra synchronisations per step are noise) a hook at its phase boundaries
+        # synchronises the device and reads the clock: sampling has no exchange, the KL construction one all-reduce, the
+        # Newton-CG one exchange per CG iteration
         marks = [time.perf_counter()]
 
         def on_phase(name):
@@ -517,14 +554,15 @@ def main():
     for _ in range(args.warmup):
         mean, _ = step(mean)
     phases.clear()
-    if comm is not None and os.environ.get("NK_BENCH_EXCHANGE_TIMER", "1") != "0":  # (world > 1, or NK_FORCE_COMM=1)
+    # (world > 1, or NK_FORCE_COMM=1; default with --full)
+    if comm is not None and os.environ.get("NK_BENCH_EXCHANGE_TIMER", "1" if args.full else "0") != "0":
         parallel.exchange_timer.enable(True)  # device events around every exchange of the sharded CG (a few per iteration)
     for k in model.counters:  # in place: the lanes of small grids (FusedModel.lanes) count into the same dictionary
         model.counters[k] = 0
     minimization.counters["cg_iterations"] = 0
     lib = L.load()
-    # live per-kernel HIP events (the roofline object); NK_BENCH_PROFILE=0 switches them off for side measurements
-    if os.environ.get("NK_BENCH_PROFILE", "1") != "0":
+    # live per-kernel HIP events (the roofline object), default with --full; NK_BENCH_PROFILE=0 switches them off there
+    if os.environ.get("NK_BENCH_PROFILE", "1" if args.full else "0") != "0":
         lib.nk_profile_enable(1)
     collect_profile()
     sync()
@@ -557,6 +595,8 @@ def main():
     prof = collect_profile()
     if comm is not None:
         elapsed = comm.max_float(elapsed, device)
+    if args.dump_outputs and rank == 0:  # (every rank holds the whole position)
+        dump_outputs(args.dump_outputs, mean, energy)
     # BASELINE configs[4]: the same model with 16 samples (two per GPU on the 8-GPU node).  With >= 2 ranks a short leg of it
     # rides along (1 warm-up + up to 3 timed steps, same barriers), so that the 8-sample strong-scaling series and the
     # 16-sample case come out of one command; on one GPU 16 samples of 1024^3 do not fit next to the CG vectors.
@@ -566,7 +606,7 @@ def main():
     # most 4 of the 16 samples (>= 4 ranks; the decision depends on the rank count only, so every rank takes the same one),
     # after the first leg's cached blocks went back to the driver.  NK_BENCH_ALSO16=force: from 2 ranks on.
     also16 = os.environ.get("NK_BENCH_ALSO16", "1")
-    if (world >= (2 if also16 == "force" else 4) and 2 * n_pairs == 8 and cfg == "C5" and also16 != "0"):
+    if args.full and world >= (2 if also16 == "force" else 4) and 2 * n_pairs == 8 and cfg == "C5" and also16 != "0":
         saved = dict(model.counters)
         k16 = max(1, min(3, args.steps))
         torch.cuda.empty_cache()
@@ -677,7 +717,7 @@ def main():
                                             achieved=round(v["bytes"] / max(v["ms"], 1e-9) / 1e6, 1), peak=HBM_PEAK_GBS,
                                             unit="GB/s", frac=round(v["bytes"] / max(v["ms"], 1e-9) / 1e6 / HBM_PEAK_GBS, 4))
                                    for k, v in sorted(spmv.items())}
-        if roofline is not None:
+        if roofline is not None and args.full:
             # "confirm on the box with a device-copy ceiling and report both" -- a 1 read + 1 write stream copy
             # of one field-sized array through the library's own chunked element-wise kernel (after the timed region)
             try:
@@ -756,7 +796,7 @@ def main():
             "comm_ms_per_cg_iteration": None if exchange is None else exchange["exchange_ms"],
             "overlap_ms": None if exchange is None else exchange["hidden_ms"],
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(counts, shape, cfg=cfg, bench_dtype=dtype, device=device, c4=c4)
             except ParityFailure as exc:  # the line is still printed -- and the run exits with code 3
@@ -764,7 +804,7 @@ def main():
                 parity_failed = True
             except Exception as exc:  # the baseline must never take the bench line down
                 line["cpu_baseline"] = {"error": repr(exc)}
-        if world == 1 and os.environ.get("NK_BENCH_API", "0") == "1" and cfg != "C4":
+        if args.full and world == 1 and os.environ.get("NK_BENCH_API", "0") == "1" and cfg != "C4":
             # the engine leg's model, vectors and cached blocks go first: the driver builds its own fused model
             data_keep, ms_tr = model.data, line["ms_per_transform_rank0"]
             del step, model, mean
