@@ -578,6 +578,49 @@ int nk_cg_update_dr_batch(int64_t n, int count, void* const* x, void* const* r, 
 int nk_cg_direction_batch(int64_t n, int count, void* const* d, const void* const* r, int dtype, double* const* scal,
                           int roll, void* stream);
 
+/* ---- non-uniform FFT: Nufft / Gridder (reference library/nft.py:40-141, which runs ducc0 on the host) on a 1-3 axis grid of
+ *      lengths nmodes, oversampled to n (nifty_amd.nufft.NufftPlan builds every array on the host, once per operator):
+ *   kernel   exponential of semicircle, phi(z) = exp(beta (sqrt(1 - (2 z / w)^2) - 1)), width w = 2 .. 16 cells; a point at
+ *            u (oversampled-grid units, [0, n)) covers the cells ceil(u - w/2) + 0 .. w-1, wrapped modulo n (n >= 2 w)
+ *   points   u[m][ndim] (fp64) SORTED by bin = tile of the oversampled grid (tile[] cells per axis, 256 in all, ntiles[] per
+ *            axis, bins in C order); perm[m] = original index of every sorted point; bin_start[nbins + 1] = first sorted
+ *            point of every bin
+ *   items    item[n_items][4] = (tile, lo, hi, slab): the positions lo .. hi-1 of the tile's point LIST -- the points of the
+ *            bins within reach[d] bins of it on every axis (wrapping, each bin once), bins in C order -- summed by one
+ *            workgroup; slab = -1: the item is the whole list and writes the tile's cells (zeros included); slab >= 0: the list
+ *            is split into chunks and the item writes scratch slab `slab` (256 complex fp64), n_split tiles split_tile[] have
+ *            their slabs split_slab[k] .. split_slab[k+1]-1 added in chunk order by a second launch.  Every tile has at least
+ *            one item, so the grid needs no memset.
+ *   corr     [nmodes_0 + nmodes_1 + nmodes_2] fp64: 1 / phi_hat(k_d / n_d) per axis, k_d = i_d - nmodes_d / 2
+ * nk_nufft_spread: grid (complex, n) = sum_j pts_j phi(l - u_j)   (pts complex [m] in the ORIGINAL order; scratch `slab` of
+ *                  2 * 256 doubles per slab, caller-owned, only read when n_split > 0)
+ * nk_nufft_interp: pts_perm[s] = sum_l grid_l phi(l - u_s)       (16 lanes per point, fixed lane tree)
+ * nk_nufft_crop  : out[i] (real, nmodes) = Re grid[k mod n] corr_0[i_0] ...        (TIMES, after nk_fftn(inverse = 1))
+ * nk_nufft_pad   : grid[l] = in[k + nmodes/2] corr (or 0), every cell written       (ADJOINT, before nk_fftn(inverse = 0));
+ *                  in real (in_complex = 0) or complex
+ * Complex data interleaved (re, im) of `dtype` (NK_F32 / NK_F64); kernel values and products in that precision, every sum in
+ * fp64.  Each output is summed by one thread or one fixed lane tree in an order fixed by the plan: no atomics,
+ * bit-reproducible.  The plan's device arrays are trusted (host-built); its geometry is validated before any launch. */
+typedef struct nk_nufft_plan {
+  int32_t ndim, w;
+  double beta;
+  int32_t n[3], nmodes[3], tile[3], ntiles[3], reach[3];
+  int64_t m;
+  const double* u;
+  const int64_t* perm;
+  const int64_t* bin_start;
+  int64_t n_items;
+  const int64_t* item;
+  int64_t n_split;
+  const int64_t* split_tile;
+  const int64_t* split_slab;
+  const double* corr;
+} nk_nufft_plan;
+int nk_nufft_spread(const nk_nufft_plan* p, const void* pts, void* grid, double* slab, int dtype, void* stream);
+int nk_nufft_interp(const nk_nufft_plan* p, const void* grid, void* pts, int dtype, void* stream);
+int nk_nufft_crop(const nk_nufft_plan* p, const void* grid, void* out, int dtype, void* stream);
+int nk_nufft_pad(const nk_nufft_plan* p, const void* in, int in_complex, void* grid, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

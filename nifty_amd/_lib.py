@@ -50,6 +50,15 @@ class TiledCsr(ctypes.Structure):
                 ("row_slot", _vp), ("loc", _vp), ("wgt", _vp)]
 
 
+class NufftPlan(ctypes.Structure):
+    """Mirror of ``struct nk_nufft_plan`` (include/niftyk.h)."""
+
+    _i32 = ctypes.c_int32
+    _fields_ = [("ndim", _i32), ("w", _i32), ("beta", _d), ("n", _i32 * 3), ("nmodes", _i32 * 3), ("tile", _i32 * 3),
+                ("ntiles", _i32 * 3), ("reach", _i32 * 3), ("m", _i64), ("u", _vp), ("perm", _vp), ("bin_start", _vp),
+                ("n_items", _i64), ("item", _vp), ("n_split", _i64), ("split_tile", _vp), ("split_slab", _vp), ("corr", _vp)]
+
+
 # name -> (restype, argtypes); the list is checked against include/niftyk.h by tests/test_abi.py
 SIGNATURES = {
     "nk_last_error": (ctypes.c_char_p, []),
@@ -115,6 +124,10 @@ SIGNATURES = {
     "nk_amp_forward": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "nk_amp_jvp": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "nk_amp_vjp": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "nk_nufft_spread": (_i, [ctypes.POINTER(NufftPlan), _vp, _vp, _vp, _i, _vp]),
+    "nk_nufft_interp": (_i, [ctypes.POINTER(NufftPlan), _vp, _vp, _i, _vp]),
+    "nk_nufft_crop": (_i, [ctypes.POINTER(NufftPlan), _vp, _vp, _i, _vp]),
+    "nk_nufft_pad": (_i, [ctypes.POINTER(NufftPlan), _vp, _i, _vp, _i, _vp]),
     # batched launches: per-member arguments are host arrays of `count` device pointers (ptr_array)
     "nk_plan_batch_ok": (_i, [_vp]),
     "nk_hartley_fused_batch": (_i, [_vp, ctypes.POINTER(Fuse), _i, _i, _vp, _vp]),

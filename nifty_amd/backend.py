@@ -527,6 +527,59 @@ class TiledMatrix:
         return ys
 
 
+class NufftDevicePlan:
+    """Device copy of a ``nufft.NufftPlan`` (the arrays of ``nk_nufft_plan``) + the slab scratch of its split spreading lists
+    (one per stream, made on first use).  The four launches of Nufft / Gridder: spread, interpolate, crop, pad."""
+
+    _keys = ("u", "perm", "bin_start", "item", "split_tile", "split_slab", "corr")
+
+    def __init__(self, plan, device):
+        self._arrays = {k: torch.from_numpy(np.ascontiguousarray(getattr(plan, k))).to(device) for k in self._keys}
+        self.n_slabs = int(plan.n_slabs)
+        i3 = lambda v: (ctypes.c_int32 * 3)(*(list(v) + [1] * (3 - len(v))))  # noqa: E731
+        self.c = L.NufftPlan(ndim=plan.ndim, w=plan.w, beta=plan.beta, n=i3(plan.n), nmodes=i3(plan.nmodes), tile=i3(plan.tile),
+                             ntiles=i3(plan.ntiles), reach=i3(plan.reach), m=plan.m, n_items=len(plan.item),
+                             n_split=len(plan.split_tile), **{k: ptr(self._arrays[k]) for k in self._keys})
+        self._scratch = {}
+
+    def _slab(self, device):
+        if self.n_slabs == 0:
+            return None
+        key = (str(device), torch.cuda.current_stream(device).cuda_stream)
+        if key not in self._scratch:
+            self._scratch[key] = torch.empty(2 * 256 * self.n_slabs, dtype=torch.float64, device=device)
+        return self._scratch[key]
+
+    def spread(self, pts, grid):
+        """grid (complex, oversampled shape) = the points' values spread with the kernel (nk_nufft_spread)"""
+        _require_device(pts, grid)
+        slab = self._slab(grid.device)
+        L.check(L.load().nk_nufft_spread(ctypes.byref(self.c), pts.data_ptr(), grid.data_ptr(), ptr(slab),
+                                         dtype_code(torch.view_as_real(grid)), _stream()), "nk_nufft_spread")
+        return grid
+
+    def interp(self, grid, pts):
+        """pts (complex [m], original order) = the grid interpolated at the points (nk_nufft_interp)"""
+        _require_device(grid, pts)
+        L.check(L.load().nk_nufft_interp(ctypes.byref(self.c), grid.data_ptr(), pts.data_ptr(),
+                                         dtype_code(torch.view_as_real(grid)), _stream()), "nk_nufft_interp")
+        return pts
+
+    def crop(self, grid, out):
+        """out (real, grid shape) = corrected real part of the centred modes of the transformed grid (nk_nufft_crop)"""
+        _require_device(grid, out)
+        L.check(L.load().nk_nufft_crop(ctypes.byref(self.c), grid.data_ptr(), out.data_ptr(), dtype_code(out), _stream()),
+                "nk_nufft_crop")
+        return out
+
+    def pad(self, x, grid):
+        """grid (complex, oversampled shape) = the corrected modes of x (real or complex, grid shape), zeros elsewhere"""
+        _require_device(x, grid)
+        L.check(L.load().nk_nufft_pad(ctypes.byref(self.c), x.data_ptr(), int(x.is_complex()), grid.data_ptr(),
+                                      dtype_code(torch.view_as_real(grid)), _stream()), "nk_nufft_pad")
+        return grid
+
+
 def spmv_t(rowptr, col, wgt, y, ncols):
     """x = R^T y by fp64 atomics, returned in y's dtype -- for callers without the transposed arrays (LOSResponse holds
     them and uses ``spmv``); order-dependent in the last bit."""
