@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cfloat>
 
 #include <cstdint>
 #include <cstdlib>
@@ -492,8 +493,9 @@ struct FPointwise {
         case 5: fv = 1.0 / v; dv = -fv * fv; break;
         case 6: fv = pow(v, param); dv = param * pow(v, param - 1.0); break;
         case 7: fv = fabs(v); dv = v == 0.0 ? (double)NAN : (v > 0.0 ? 1.0 : -1.0); break;
-        case 8: fv = log1p(v); dv = 1.0 / (1.0 + v); break;
-        case 9: fv = expm1(v); dv = fv + 1.0; break;
+        // log1p and expm1 have the sign of v; copysign keeps log1p(-0) = expm1(-0) = -0, which the device library returns as +0
+        case 8: fv = copysign(log1p(v), v); dv = 1.0 / (1.0 + v); break;
+        case 9: fv = copysign(expm1(v), v); dv = fv + 1.0; break;
         case 10: fv = atan(v); dv = 1.0 / (1.0 + v * v); break;
         case 11: fv = sin(v); dv = cos(v); break;
         case 12: fv = cos(v); dv = -sin(v); break;
@@ -790,6 +792,11 @@ extern "C" int nk_binary(int op, int64_t n, const void* a, double ascalar, const
 }
 
 // ---- complex element-wise algebra on interleaved (re, im) arrays --------------------------------------------------
+// exponent of max(|x|, |y|) (ilogb), 0 for 0, inf and NaN: scalbn(., -k) brings a complex number to a modulus in [1, 2 sqrt 2)
+__device__ __forceinline__ int nk_cexpo(double x, double y) {
+  const double m = fmax(fabs(x), fabs(y));
+  return m > 0.0 && m <= DBL_MAX ? ilogb(m) : 0;
+}
 // out = a (*|/) b with b optionally conjugated; an operand is a complex array of n elements, a REAL array of n elements
 // (kind 1) or a complex scalar (kind 2).  DiagonalOperator with a complex diagonal and its adjoint / inverse modes
 // (diagonal_operator.py:194-214), complex residual weights of GaussianEnergy (energy_operators.py:517-595).
@@ -812,9 +819,12 @@ struct FCplxMulDiv {
     else br = bsr, bi = bsi;
     if (conj_b) bi = -bi;
     double re, im;
-    if (divide) {
+    if (divide) {  // each operand scaled by an exact power of two to a largest component in [1, 2): no square overflows or
+                   // underflows, the quotient is scaled back once
+      const int ka = nk_cexpo(ar, ai), kb = nk_cexpo(br, bi);
+      ar = scalbn(ar, -ka), ai = scalbn(ai, -ka), br = scalbn(br, -kb), bi = scalbn(bi, -kb);
       const double den = br * br + bi * bi;
-      re = (ar * br + ai * bi) / den, im = (ai * br - ar * bi) / den;
+      re = scalbn((ar * br + ai * bi) / den, ka - kb), im = scalbn((ai * br - ar * bi) / den, ka - kb);
     } else {
       re = ar * br - ai * bi, im = ar * bi + ai * br;
     }
@@ -845,13 +855,32 @@ struct FCplxPointwise {
     double fr = re, fi = -im;
     switch (fn) {
       case 0: { const double e = exp(re); fr = e * cos(im), fi = e * sin(im); } break;
-      case 1: fr = 0.5 * log(re * re + im * im), fi = atan2(im, re); break;
-      case 2: {
-        const double r = hypot(re, im);
-        fr = sqrt(0.5 * (r + re));
-        fi = copysign(sqrt(0.5 * (r - re)), im);
+      case 1: {  // log|z|; near |z| = 1 as log1p(|z|^2 - 1) / 2 with (a - 1)(a + 1) exact in its first factor (Sterbenz)
+        const double a = fmax(fabs(re), fabs(im)), b = fmin(fabs(re), fabs(im)), h = hypot(re, im);
+        fr = h > 0.7071 && h < 1.4142 ? 0.5 * log1p((a - 1.0) * (a + 1.0) + b * b) : log(h);
+        fi = atan2(im, re);
       } break;
-      case 3: { const double den = re * re + im * im; fr = re / den, fi = -im / den; } break;
+      case 2: {  // principal root: t = sqrt((|re| + |z|) / 2) is the larger component, |im| / (2t) the other -- no cancellation
+        const double ax = fabs(re), ay = fabs(im);
+        const int k = nk_cexpo(re, im) & ~1;  // an even exponent: |z| scaled to [1, 4), its root scaled back by 2^(k/2)
+        if (ax == 0.0 && ay == 0.0) {
+          fr = 0.0, fi = im;
+        } else if (!(fmax(ax, ay) <= DBL_MAX)) {  // an infinite component (or NaN in both): the direct formula, C99 values
+          const double r = hypot(re, im);
+          fr = sqrt(0.5 * (r + re)), fi = copysign(sqrt(0.5 * (r - re)), im);
+        } else {
+          const double sx = scalbn(ax, -k), sy = scalbn(ay, -k);
+          const double t = scalbn(sqrt(0.5 * (sx + hypot(sx, sy))), k / 2);
+          const double o = ay / (2.0 * t);
+          fr = re >= 0.0 ? t : o;
+          fi = copysign(re >= 0.0 ? o : t, im);
+        }
+      } break;
+      case 3: {  // 1/z = conj(z) / |z|^2 with z scaled by an exact power of two to a largest component in [1, 2)
+        const int k = nk_cexpo(re, im);
+        const double sr = scalbn(re, -k), si = scalbn(im, -k), den = sr * sr + si * si;
+        fr = scalbn(sr / den, -k), fi = scalbn(-si / den, -k);
+      } break;
       case 5: out[c] = (T)hypot(re, im); return;
       default: break;
     }
