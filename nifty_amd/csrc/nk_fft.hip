@@ -152,20 +152,21 @@ __global__ void __launch_bounds__((FinalTile<T, NL, EC, COUPLES ? 2 : 1>::THREAD
   if constexpr (COUPLES && (EC == 2 || EC == -1)) nk_flush_wmax(f, wmax);  // 3-D launches only (nk_final_with_slots)
 }
 
+// the launcher `launch(std::integral_constant<int, n>)` of a fast length (nk_with_fast_size); any other length is an error
+template <typename F>
+static int nk_dispatch_fast(int n, const char* no_kernel, F&& launch) {
+  if (!nk_fast_size(n)) return nk_set_error(NK_ERR_UNSUPPORTED, no_kernel);
+  return nk_with_fast_size(n, (int)NK_ERR_UNSUPPORTED, launch);
+}
+
 template <typename T, int NL, bool COUPLES, int EC, int PAIR = 0>
 static int nk_launch_final_c(NkPassF pf, const NkFuse& f, const C2<T>* tw, const C2<T>* work, hipStream_t st) {
   using CT = FinalTile<T, NL, EC, COUPLES ? 2 : 1>;
   static_assert(!COUPLES || CT::TILE >= 2, "the couple (b0, M - b0) must live in one workgroup");
-  auto kern = k2_final<T, NL, COUPLES, EC, PAIR>;
-  static unsigned long long attr_mask = 0;  // per-device attribute
-  if (CT::LDS_BYTES > 64 * 1024 && nk_first_on_device(attr_mask)) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, CT::LDS_BYTES);
-    if (e != hipSuccess) return nk_set_hip_error(e, "hipFuncSetAttribute(k2_final)");
-  }
   pf.tiles_per_a = (COUPLES && pf.A > 1 && CT::TILE >= 2) ? (pf.M / 2 + 1 + CT::TILE / 2 - 1) / (CT::TILE / 2)
                                                : (pf.M + CT::TILE - 1) / CT::TILE;
   int64_t blocks = (int64_t)pf.g.batch * (pf.A / 2 + 1) * pf.tiles_per_a;
-  static const int xmap_env = nk_env_int("NK_XMAP", NK_XMAP_DEFAULT);
+  const int xmap_env = nk_knobs().xmap;
   NkFuse fs = f;
   pf.blk0 = 0;
   if (pf.a_cnt > 0) {
@@ -193,15 +194,14 @@ static int nk_launch_final_c(NkPassF pf, const NkFuse& f, const C2<T>* tw, const
       return nk_set_error(NK_ERR_UNSUPPORTED, "batched final pass: no batched twin of this kernel class");
     }
   }
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(CT::THREADS), CT::LDS_BYTES, st, pf, fs, tw, work, xmap_env & 4);
-  return nk_check_launch("k2_final");
+  return nk_launch<k2_final<T, NL, COUPLES, EC, PAIR>>("k2_final", dim3((unsigned)blocks), dim3(CT::THREADS), CT::LDS_BYTES, st, pf, fs, tw,
+                                                       work, xmap_env & 4);
 }
 
 // the scatter epilogue (VJP) runs on line couples (8 sign-flip images per atomic); everything else on plain pairs
 template <typename T, int NL>
 static int nk_launch_final(const NkPassF& pf, const NkFuse& f, const C2<T>* tw, const C2<T>* work, hipStream_t st) {
-  static const int generic = nk_env_int("NK_EC_GENERIC", 0);
-  if (generic && !f.field_octant) {
+  if (nk_knobs().ec_generic && !f.field_octant) {
     if (f.epi == NK_EPI_VJP) return nk_launch_final_c<T, NL, true, -1>(pf, f, tw, work, st);
     return nk_launch_final_c<T, NL, false, -1>(pf, f, tw, work, st);
   }
@@ -237,73 +237,39 @@ static int nk_launch_final3(const NkPassF& pf, const NkFuse& f, const C2<T>* tw,
 template <typename T>
 static int nk_dispatch_final3(int nl, const NkPassF& pf, const NkFuse& f, const C2<T>* tw, const C2<T>* work,
                               hipStream_t st) {
-  switch (nl) {
-#define NK_CASE(NN) \
-  case NN:          \
-    return nk_launch_final3<T, NN>(pf, f, tw, work, st);
-    NK_FAST_SIZES(NK_CASE)
-#undef NK_CASE
-  }
-  return nk_set_error(NK_ERR_UNSUPPORTED, "no fast final pass for this length");
+  return nk_dispatch_fast(nl, "no fast final pass for this length", [&](auto N) { return nk_launch_final3<T, N()>(pf, f, tw, work, st); });
 }
 
 template <typename T>
 static int nk_dispatch_final_pair(int nl, const NkPassF& pf, const NkFuse& fa, const NkFuse& fb, const C2<T>* tw,
                                   const C2<T>* worka, const C2<T>* workb, hipStream_t st) {
-  switch (nl) {
-#define NK_CASE(NN) \
-  case NN:          \
-    return nk_launch_final_pair<T, NN>(pf, fa, fb, tw, worka, workb, st);
-    NK_FAST_SIZES(NK_CASE)
-#undef NK_CASE
-  }
-  return nk_set_error(NK_ERR_UNSUPPORTED, "no fast final pass for this length");
+  return nk_dispatch_fast(nl, "no fast final pass for this length",
+                          [&](auto N) { return nk_launch_final_pair<T, N()>(pf, fa, fb, tw, worka, workb, st); });
 }
 
 template <typename T>
 static int nk_dispatch_final(int nl, const NkPassF& pf, const NkFuse& f, const C2<T>* tw, const C2<T>* work,
                              hipStream_t st) {
-  switch (nl) {
-#define NK_CASE(NN) \
-  case NN:          \
-    return nk_launch_final<T, NN>(pf, f, tw, work, st);
-    NK_FAST_SIZES(NK_CASE)
-#undef NK_CASE
-  }
-  return nk_set_error(NK_ERR_UNSUPPORTED, "no fast final pass for this length");
+  return nk_dispatch_fast(nl, "no fast final pass for this length", [&](auto N) { return nk_launch_final<T, N()>(pf, f, tw, work, st); });
 }
 
 template <typename T, int H, bool IS_1D>
 static int nk_launch_contig(const NkPassA& pa, const NkFuse& f, const C2<T>* tw, const C2<T>* twr, C2<T>* work,
                             hipStream_t st) {
   using CT = ContigTile<T, H>;
-  auto kern = k2_contig<T, H, IS_1D>;
-  static unsigned long long attr_mask = 0;  // per-device attribute
-  if (CT::LDS_BYTES > 64 * 1024 && nk_first_on_device(attr_mask)) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, CT::LDS_BYTES);
-    if (e != hipSuccess) return nk_set_hip_error(e, "hipFuncSetAttribute(k2_contig)");
-  }
   const int64_t blocks = (pa.nlines + CT::TILE - 1) / CT::TILE;
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(CT::THREADS), CT::LDS_BYTES, st, pa, f, tw, twr, work);
-  return nk_check_launch("k2_contig");
+  return nk_launch<k2_contig<T, H, IS_1D>>("k2_contig", dim3((unsigned)blocks), dim3(CT::THREADS), CT::LDS_BYTES, st, pa, f, tw, twr, work);
 }
 
 template <typename T, int N, int MODE, int PC>
 static int nk_launch_strided_pc(NkPassS ps, const NkFuse& f, const C2<T>* tw, C2<T>* work, C2<T>* scratch, hipStream_t st) {
   using ST = StridedTile<T, N, nk_strided_cx<MODE, PC>(), MODE>;
-  auto kern = k2_strided<T, N, MODE, PC>;
-  static unsigned long long attr_mask = 0;  // per-device attribute
-  if (ST::LDS_TOTAL > 64 * 1024 && nk_first_on_device(attr_mask)) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, ST::LDS_TOTAL);
-    if (e != hipSuccess) return nk_set_hip_error(e, "hipFuncSetAttribute(k2_strided)");
-  }
   ps.tl.tile = ST::TILE;
   ps.tl.dtile = nk_make_div(ST::TILE);
   ps.tiles_per_slab = (int)(ps.inner / ST::TILE);
   const int64_t blocks = ps.outer * ps.tiles_per_slab;
-  static const int xmap_env = nk_env_int("NK_XMAP", NK_XMAP_DEFAULT);
-  // in-place pass: bit 1 for every layout, bit 3 for the middle-axis pass of the sandwich only (blo > 0: 1.66 -> 1.62 ms at
-  // 1024^3 fp32, while the in-place pass of the six-pass pipeline loses 8 % with it)
+  const int xmap_env = nk_knobs().xmap;
+  // in-place pass: bit 1 for every layout, bit 3 for the middle-axis pass of the sandwich only (blo > 0)
   const int xmap = MODE == 3 ? (xmap_env & 1) : ((xmap_env & 2) | ((xmap_env & 8) && ps.blo > 0 ? 2 : 0));
   if (t_batch != nullptr) {
     if constexpr (MODE != 3 || !nk_twin_strided<N, PC>()) {
@@ -312,21 +278,15 @@ static int nk_launch_strided_pc(NkPassS ps, const NkFuse& f, const C2<T>* tw, C2
       return nk_twin_launch_strided<T, N, PC>(ps, blocks, tw, xmap, st);
     }
   }
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(ST::THREADS), ST::LDS_TOTAL, st, ps, f, tw, work, scratch, xmap);
-  return nk_check_launch("k2_strided");
+  return nk_launch<k2_strided<T, N, MODE, PC>>("k2_strided", dim3((unsigned)blocks), dim3(ST::THREADS), ST::LDS_TOTAL, st, ps, f, tw, work,
+                                               scratch, xmap);
 }
 
 template <typename T, bool IS_1D>
 static int nk_dispatch_contig(int h, const NkPassA& pa, const NkFuse& f, const C2<T>* tw, const C2<T>* twr, C2<T>* work,
                               hipStream_t st) {
-  switch (h) {
-#define NK_CASE(NN) \
-  case NN:          \
-    return nk_launch_contig<T, NN, IS_1D>(pa, f, tw, twr, work, st);
-    NK_FAST_SIZES(NK_CASE)
-#undef NK_CASE
-  }
-  return nk_set_error(NK_ERR_UNSUPPORTED, "no fast contiguous pass for this length");
+  return nk_dispatch_fast(h, "no fast contiguous pass for this length",
+                          [&](auto N) { return nk_launch_contig<T, N(), IS_1D>(pa, f, tw, twr, work, st); });
 }
 
 // pick the compile-time prologue specialisation (first pass only)
@@ -351,14 +311,8 @@ static int nk_launch_strided(const NkPassS& ps, const NkFuse& f, const C2<T>* tw
 template <typename T, int MODE>
 static int nk_dispatch_strided(int n, const NkPassS& ps, const NkFuse& f, const C2<T>* tw, C2<T>* work, C2<T>* scratch,
                                hipStream_t st) {
-  switch (n) {
-#define NK_CASE(NN) \
-  case NN:          \
-    return nk_launch_strided<T, NN, MODE>(ps, f, tw, work, scratch, st);
-    NK_FAST_SIZES(NK_CASE)
-#undef NK_CASE
-  }
-  return nk_set_error(NK_ERR_UNSUPPORTED, "no fast strided pass for this length");
+  return nk_dispatch_fast(n, "no fast strided pass for this length",
+                          [&](auto N) { return nk_launch_strided<T, N(), MODE>(ps, f, tw, work, scratch, st); });
 }
 
 // ---- sandwich pipeline (nk_fft3.h) ------------------------------------------------------------------------
@@ -418,7 +372,7 @@ __global__ void __launch_bounds__((Contig3Tile<T, H>::QTHREADS)) __attribute__((
   nk_contig3_body<T, H, 4, PC, true>(ex, p, f, (int64_t)blockIdx.x + p.blk0, (T*)smem, tw, twr, work, (int)blockIdx.y);
 }
 template <typename T, int H, int PC>
-static auto nk_quad_kernel() {
+static constexpr auto nk_quad_kernel() {
   if constexpr (nk_quad_max_waves<T, PC>() < 8)
     return k3_contig_quad_w<T, H, PC, nk_quad_max_waves<T, PC>()>;
   else
@@ -429,20 +383,7 @@ template <typename T, int H, int PC>
 static int nk_launch_contig3(const NkPass3& p3, const NkFuse& f, const C2<T>* tw, const C2<T>* twr, C2<T>* work, hipStream_t st) {
   using CT = Contig3Tile<T, H>;
   if constexpr ((PC == 4 || PC == 5 || PC == 7 || PC == 8) && CT::QUAD_OK) {
-    // NK_CONTIG_QUAD: 1 (default) = QUAD workgroups for every launch on a 3-D grid, 2 = for the staged launches of a
-    // pipelined sandwich only, 0 = never.  QUAD cuts the FETCH of the JVP class from 15.2 to 10.1 GB per launch at 1024^3
-    // fp32 (the octant lines of a[pidx] / da[pidx] are read once per workgroup instead of once per row); on an otherwise idle
-    // GPU the pass takes the same time either way (3.59-3.63 vs 3.60-3.61 ms per launch over a bench step, identical bits:
-    // the extra fetches were served by L2 / Infinity Cache) -- the smaller footprint on the fabric is what a rank wants
-    // while its RCCL exchange runs beside the pass.
-    static const int quad = nk_env_int("NK_CONTIG_QUAD", 1);
-    if ((quad == 1 || (quad == 2 && p3.nblk > 0)) && p3.g.ndim == 3) {
-      auto qkern = nk_quad_kernel<T, H, PC>();
-      static unsigned long long qattr_mask = 0;
-      if (CT::QLDS_BYTES > 64 * 1024 && nk_first_on_device(qattr_mask)) {
-        hipError_t e = hipFuncSetAttribute((const void*)qkern, hipFuncAttributeMaxDynamicSharedMemorySize, CT::QLDS_BYTES);
-        if (e != hipSuccess) return nk_set_hip_error(e, "hipFuncSetAttribute(k3_contig_quad)");
-      }
+    if (nk_contig3_quad(p3.nblk, p3.g.ndim)) {  // (NK_CONTIG_QUAD, nk_plan.h)
       const int64_t batch = p3.nlines / ((int64_t)p3.g.na * p3.g.nm);
       int64_t qblocks = batch * (p3.g.na / 2 + 1) * (p3.g.nm / 2 + 1);
       if (p3.nblk > 0) {  // one stage of a pipelined sandwich
@@ -455,24 +396,16 @@ static int nk_launch_contig3(const NkPass3& p3, const NkFuse& f, const C2<T>* tw
       if (gx > 0x7fffffffLL || batch > 65535) return nk_set_error(NK_ERR_UNSUPPORTED, "too many lines for one launch");
       NkPass3 pq = p3;
       pq.dmh = nk_make_div(p3.g.nm / 2 + 1);
-      hipLaunchKernelGGL(qkern, dim3((unsigned)gx, (unsigned)(p3.nblk > 0 ? 1 : batch)), dim3(CT::QTHREADS), CT::QLDS_BYTES, st, pq, f,
-                         tw, twr, work);
-      return nk_check_launch("k3_contig_quad");
+      return nk_launch<nk_quad_kernel<T, H, PC>()>("k3_contig_quad", dim3((unsigned)gx, (unsigned)(p3.nblk > 0 ? 1 : batch)), dim3(CT::QTHREADS),
+                                                   CT::QLDS_BYTES, st, pq, f, tw, twr, work);
     }
   }
   if (p3.nblk > 0)
     return nk_set_error(NK_ERR_UNSUPPORTED, "nk_fuse.pipe_chunks: the staged first pass exists for the QUAD launches only (3-D plan, "
                                              "octant prologue classes, last axis <= 2048 fp32, NK_CONTIG_QUAD != 0)");
-  auto kern = k3_contig<T, H, PC>;
-  static unsigned long long attr_mask = 0;  // per-device attribute
-  if (CT::LDS_BYTES > 64 * 1024 && nk_first_on_device(attr_mask)) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, CT::LDS_BYTES);
-    if (e != hipSuccess) return nk_set_hip_error(e, "hipFuncSetAttribute(k3_contig)");
-  }
   const int64_t blocks = (p3.nlines + CT::TILE - 1) / CT::TILE;
   if (blocks > 0x7fffffffLL) return nk_set_error(NK_ERR_UNSUPPORTED, "too many lines for one launch");
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(CT::THREADS), CT::LDS_BYTES, st, p3, f, tw, twr, work);
-  return nk_check_launch("k3_contig");
+  return nk_launch<k3_contig<T, H, PC>>("k3_contig", dim3((unsigned)blocks), dim3(CT::THREADS), CT::LDS_BYTES, st, p3, f, tw, twr, work);
 }
 
 template <typename T, int H>
@@ -489,14 +422,8 @@ static int nk_launch_contig3_pc(const NkPass3& p3, const NkFuse& f, const C2<T>*
 template <typename T>
 static int nk_dispatch_contig3(int h, const NkPass3& p3, const NkFuse& f, const C2<T>* tw, const C2<T>* twr, C2<T>* work,
                                hipStream_t st) {
-  switch (h) {
-#define NK_CASE(NN) \
-  case NN:          \
-    return nk_launch_contig3_pc<T, NN>(p3, f, tw, twr, work, st);
-    NK_FAST_SIZES(NK_CASE)
-#undef NK_CASE
-  }
-  return nk_set_error(NK_ERR_UNSUPPORTED, "no fast contiguous pass for this length");
+  return nk_dispatch_fast(h, "no fast contiguous pass for this length",
+                          [&](auto N) { return nk_launch_contig3_pc<T, N()>(p3, f, tw, twr, work, st); });
 }
 
 #ifndef NK_MID_CX
@@ -551,17 +478,10 @@ __global__ void __launch_bounds__((MidCfg<T, N, MF>::ST::THREADS), (MidCfg<T, N,
 template <typename T, int N, bool MF>
 static int nk_launch_mid(NkPassM pm, const NkFuse& f, const C2<T>* tw, C2<T>* work, hipStream_t st) {
   using ST = typename MidCfg<T, N, MF>::ST;
-  auto kern = k3_mid<T, N, MF>;
-  static unsigned long long attr_mask = 0;  // per-device attribute
-  if (ST::LDS_TOTAL > 64 * 1024 && nk_first_on_device(attr_mask)) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, ST::LDS_TOTAL);
-    if (e != hipSuccess) return nk_set_hip_error(e, "hipFuncSetAttribute(k3_mid)");
-  }
   pm.s.tl.tile = ST::TILE;
   pm.s.tl.dtile = nk_make_div(ST::TILE);
   pm.s.tiles_per_slab = (int)(pm.s.inner / ST::TILE);
   const int64_t blocks = pm.s.outer * pm.s.tiles_per_slab;
-  static const int xmap_env = nk_env_int("NK_XMAP", NK_XMAP_DEFAULT);
   // persistent: as many workgroups as the device keeps resident (LDS decides: one or two per CU)
   int64_t grid = blocks;
   if (NK_MID_PF) {
@@ -571,30 +491,19 @@ static int nk_launch_mid(NkPassM pm, const NkFuse& f, const C2<T>* tw, C2<T>* wo
       hipDeviceProp_t prop;
       cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
     }
-    static const int per_cu_env = nk_env_int("NK_MID_WG_PER_CU", 0);
+    const int per_cu_env = nk_knobs().mid_wg_per_cu;
     const int per_cu = per_cu_env > 0 ? per_cu_env : (ST::LDS_TOTAL <= 80 * 1024 && ST::THREADS <= 512 ? 2 : 1);
     if (grid > (int64_t)cus * per_cu) grid = (int64_t)cus * per_cu;
   }
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(ST::THREADS), ST::LDS_TOTAL, st, pm, f, tw, work, blocks, xmap_env & 2);
-  return nk_check_launch("k3_mid");
+  return nk_launch<k3_mid<T, N, MF>>("k3_mid", dim3((unsigned)grid), dim3(ST::THREADS), ST::LDS_TOTAL, st, pm, f, tw, work, blocks,
+                                     nk_knobs().xmap & 2);
 }
 
 template <typename T>
 static int nk_dispatch_mid(int n, const NkPassM& pm, const NkFuse& f, const C2<T>* tw, C2<T>* work, hipStream_t st) {
-  switch (n) {
-#define NK_CASE(NN) \
-  case NN:          \
-    return f.mul ? nk_launch_mid<T, NN, true>(pm, f, tw, work, st) : nk_launch_mid<T, NN, false>(pm, f, tw, work, st);
-    NK_FAST_SIZES(NK_CASE)
-#undef NK_CASE
-  }
-  return nk_set_error(NK_ERR_UNSUPPORTED, "no fast strided pass for this length");
-}
-
-static bool nk_fast_enabled() {
-  static int v = -1;
-  if (v < 0) v = nk_env_int("NK_FAST", 1) ? 1 : 0;
-  return v == 1;
+  return nk_dispatch_fast(n, "no fast strided pass for this length", [&](auto N) {
+    return f.mul ? nk_launch_mid<T, N(), true>(pm, f, tw, work, st) : nk_launch_mid<T, N(), false>(pm, f, tw, work, st);
+  });
 }
 
 // ---- c2c passes -----------------------------------------------------------------------------------
@@ -823,7 +732,7 @@ extern "C" int nk_plan_destroy(nk_plan* P) {
 static bool nk_plan_uses_pipeline2(const nk_plan* P) {
   const NkHostPlan& hp = P->hp;
   const bool f32 = hp.dtype == NK_F32;
-  if (!nk_fast_enabled() || nk_env_int("NK_PIPELINE", 2) != 2 || hp.g.ndim < 2 || !nk_fast_size(hp.g.nl)) return false;
+  if (!nk_knobs().fast || nk_knobs().pipeline != 2 || hp.g.ndim < 2 || !nk_fast_size(hp.g.nl)) return false;
   const bool first_ok = f32 ? nk_fast_strided_ok<float>(hp.g.na, hp.pc.inner) : nk_fast_strided_ok<double>(hp.g.na, hp.pc.inner);
   const bool mid_ok = hp.g.ndim == 2 || (f32 ? nk_fast_strided_ok<float>(hp.g.nm, hp.pb.inner)
                                              : nk_fast_strided_ok<double>(hp.g.nm, hp.pb.inner));
@@ -1005,7 +914,7 @@ static int nk_run_hartley(const nk_plan* P, const NkFuse& f, int convention, voi
   const C2<T>* twr = (const C2<T>*)P->d_twr_a;
   const int64_t blocks_a = (pa.nlines + pa.tl.tile - 1) / pa.tl.tile;
   if (blocks_a > 0x7fffffffLL) return nk_set_error(NK_ERR_UNSUPPORTED, "too many lines for one launch");
-  const bool fast = nk_fast_enabled();
+  const bool fast = nk_knobs().fast != 0;
   // Energy / curvature sums of the kernels below (everything but the strided-first pipeline, which brings its own slot
   // handling): one slot per WAVEFRONT in the workspace's slot area, folded in a fixed order afterwards -- bit-reproducible
   // like the fast path (round 3; until then one fp64 atomic per workgroup).  Without a workspace (1-D calls may omit it) or
@@ -1052,15 +961,10 @@ static int nk_run_hartley(const nk_plan* P, const NkFuse& f, int convention, voi
   int rc;
   // ---- strided-first pipeline (default when every axis has a specialised kernel): strided c2c passes on the
   //      real array viewed as complex pairs, then ONE contiguous final pass per line pair (k, -k)
-  static const int pipeline = nk_env_int("NK_PIPELINE", 2);
-  if (fast && pipeline == 2 && nk_fast_size(hp.g.nl) && nk_fast_strided_ok<T>(hp.g.na, hp.pc.inner) &&
+  if (fast && nk_knobs().pipeline == 2 && nk_fast_size(hp.g.nl) && nk_fast_strided_ok<T>(hp.g.na, hp.pc.inner) &&
       (hp.g.ndim == 2 || nk_fast_strided_ok<T>(hp.g.nm, hp.pb.inner))) {
-    // 3-D work array: natural [batch][first] slabs whose stride is padded by NK_WORK_PAD elements -- the in-place pass
-    // over the first axis otherwise walks an exact power-of-two stride (nm*nl/2 elements: HBM channel aliasing,
-    // 2.9 -> 2.05 ms at 1024^3 fp32).  NK_WORK_BLO=1 selects the transposed slab order [batch][mid][first][last/2]
-    // instead (second pass at stride nl/2, first-pass stores at the big stride): measured slower in total.
-    static const int work_blo = nk_env_int("NK_WORK_BLO", 0), work_pad = nk_env_int("NK_WORK_PAD", 2080);
-    NkPipe2 q = nk_pipe2_setup(hp, pa.g.sign, work_blo, work_pad);
+    // 3-D work array: natural [batch][first] slabs with a padded stride (NK_WORK_PAD, NK_WORK_BLO: nk_plan.h)
+    NkPipe2 q = nk_pipe2_setup(hp, pa.g.sign, nk_knobs().work_blo, nk_knobs().work_pad);
     // per-thread address parts are 32-bit: (threads per line) * (row stride) must stay below 2^31 elements
     {
       const int64_t smax = q.s1.ss > q.s0.inner ? q.s1.ss : q.s0.inner;
@@ -1088,8 +992,7 @@ static int nk_run_hartley(const nk_plan* P, const NkFuse& f, int convention, voi
     if (rc != NK_OK) return rc;
     const NkPassF& pf = q.pf;
     ProfScope ps(st, 3, f.pro, f.epi);
-    static const int skip_final = nk_env_int("NK_SKIP_FINAL", 0);  // debugging aid
-    if (skip_final) return NK_OK;
+    if (nk_knobs().skip_final) return NK_OK;  // debugging aid
     return nk_final_with_slots(hp, workspace, f, st, [&](const NkFuse& f2) {
       return nk_dispatch_final<T>(hp.g.nl, pf, f2, (const C2<T>*)P->d_tw_f, (const C2<T>*)work, st);
     });
@@ -1223,10 +1126,9 @@ static bool nk_same_class(const nk_fuse& a, const nk_fuse& b) {
 }
 
 extern "C" int nk_plan_batch_ok(const nk_plan* P) {
-  if (!P || !nk_plan_uses_pipeline2(P) || !nk_fast_enabled()) return 0;
+  if (!P || !nk_plan_uses_pipeline2(P)) return 0;  // (fast path on, NK_PIPELINE == 2, fast last axis)
   const NkHostPlan& hp = P->hp;
-  static const int pipeline = nk_env_int("NK_PIPELINE", 2);
-  if (hp.g.ndim != 2 || hp.g.batch != 1 || pipeline != 2 || !nk_fast_size(hp.g.nl)) return 0;
+  if (hp.g.ndim != 2 || hp.g.batch != 1) return 0;
   return P->hp.dtype == NK_F32 ? nk_fast_strided_ok<float>(hp.g.na, hp.pc.inner) : nk_fast_strided_ok<double>(hp.g.na, hp.pc.inner);
 }
 
@@ -1242,8 +1144,7 @@ static int nk_run_hartley_batch(const nk_plan* P, const nk_fuse* fuse, int count
     bc.wa.work[m] = workspace[k];
     bc.wa.scratch[m] = (char*)workspace[k] + (hp.work_bytes + 255) / 256 * 256;
   }
-  static const int work_blo = nk_env_int("NK_WORK_BLO", 0), work_pad = nk_env_int("NK_WORK_PAD", 2080);
-  NkPipe2 q = nk_pipe2_setup(hp, convention == NK_HARTLEY_CANONICAL ? -1 : 1, work_blo, work_pad);
+  NkPipe2 q = nk_pipe2_setup(hp, convention == NK_HARTLEY_CANONICAL ? -1 : 1, nk_knobs().work_blo, nk_knobs().work_pad);
   {
     const int64_t smax = q.s1.ss > q.s0.inner ? q.s1.ss : q.s0.inner;
     if (128 * (smax > q.s1.inner ? smax : q.s1.inner) * (int64_t)sizeof(C2<T>) >= ((int64_t)1 << 32))
@@ -1343,21 +1244,14 @@ extern "C" int nk_plan_sandwich(const nk_plan* P) {
 
 template <typename T>
 static bool nk_contig3_quad_ok(int h) {
-  switch (h) {
-#define NK_CASE(NN) \
-  case NN:          \
-    return Contig3Tile<T, NN>::QUAD_OK;
-    NK_FAST_SIZES(NK_CASE)
-#undef NK_CASE
-  }
-  return false;
+  return nk_with_fast_size(h, false, [](auto N) { return (bool)Contig3Tile<T, N()>::QUAD_OK; });
 }
 // 1 if nk_hartley_sandwich on this plan accepts nk_fuse.pipe_chunks == chunks (with an octant amplitude prologue)
 extern "C" int nk_plan_pipe_ok(const nk_plan* P, int chunks) {
   if (!nk_plan_sandwich(P) || chunks < 2 || (chunks & 1)) return 0;
   const NkGeom& g = P->hp.g;
   if (g.ndim != 3 || g.batch != 1 || g.na % chunks != 0) return 0;
-  if (!nk_env_int("NK_CONTIG_QUAD", 1) || (nk_env_int("NK_XMAP", NK_XMAP_DEFAULT) & 4)) return 0;
+  if (!nk_knobs().contig_quad || (nk_knobs().xmap & 4)) return 0;
   return (P->hp.dtype == NK_F32 ? nk_contig3_quad_ok<float>(g.h) : nk_contig3_quad_ok<double>(g.h)) ? 1 : 0;
 }
 
@@ -1366,7 +1260,7 @@ static int nk_run_sandwich(const nk_plan* P, const NkFuse& f, double scale_first
                            bool with_final = true, NkPipe3* q_out = nullptr) {
   const NkHostPlan& hp = P->hp;
   const int sign = convention == NK_HARTLEY_CANONICAL ? -1 : 1;
-  static const int work_pad = nk_env_int("NK_WORK_PAD", 2080);
+  const int work_pad = nk_knobs().work_pad;
   const NkPipe3 q = nk_pipe3_setup<T>(hp, sign, work_pad, scale_first * (f.mul_scalar != 0.0 ? f.mul_scalar : 1.0));
   if (q_out) *q_out = q;
   if (nk_pipe3_work_elems(hp.g, nk_pipe3_colpad<T>(), work_pad) * sizeof(C2<T>) > hp.work_bytes)

@@ -518,10 +518,7 @@ NK_HD void nk_tw_to_lds(const C2<T>* __restrict__ tw_global, C2<T>* tw_lds, int 
 // array (adjacent 128 B pieces) meet in one XCD's L2 / TLB instead of being spread over all eight.  A pure copy with
 // the first pass's access pattern (1024 rows x 128 B at 4 KiB stride, 1024^3 fp32) runs at 4.77 TB/s in natural
 // order and at 5.51 TB/s with this order (tools/micro/copy_bench.hip).  A bijection of [0, nb); speed only.
-#ifndef NK_XMAP_DEFAULT
-#define NK_XMAP_DEFAULT 9  // bit 0: first strided pass, bit 1: every in-place strided pass, bit 2: final pass, bit 3: the
-                           // in-place middle-axis pass of the sandwich
-#endif
+// Which passes use it: NkKnobs::xmap (nk_plan.h).
 NK_HD int64_t nk_xcd_contig(int64_t blk, int64_t nb) {
   const int64_t q = nb / 8, r = nb % 8;
   const int64_t x = blk % 8, i = blk / 8;
@@ -1569,24 +1566,27 @@ NK_HD void nk_final_body(Exec& ex, const NkPassF& p, const NkFuse& f_in, int64_t
 #define NK_FAST_SIZES(X) X(64) X(128) X(256) X(512) X(1024) X(2048) X(4096)
 #endif
 
-static inline bool nk_fast_size(int n) {
-#define NK_CASE(NN) \
-  if (n == NN) return true;
-  NK_FAST_SIZES(NK_CASE)
-#undef NK_CASE
-  return false;
-}
-template <typename T>
-static inline int nk_fast_strided_tile(int n) {
+// From a run-time length to a template argument: f(std::integral_constant<int, N>{}) for the N of NK_FAST_SIZES that
+// equals n -- inside a generic lambda `[&](auto N) { return launcher<T, N()>(...); }` -- or `otherwise` for any other length.
+template <typename R, typename F>
+static inline R nk_with_fast_size(int n, R otherwise, F&& f) {
   switch (n) {
 #define NK_CASE(NN) \
   case NN:          \
-    return StridedTile<T, NN>::TILE > StridedTile<T, NN, false, 0>::TILE ? StridedTile<T, NN>::TILE : StridedTile<T, NN, false, 0>::TILE;
+    return f(std::integral_constant<int, NN>{});
     NK_FAST_SIZES(NK_CASE)
 #undef NK_CASE
-    default:
-      return 0;
   }
+  return otherwise;
+}
+static inline bool nk_fast_size(int n) {
+  return nk_with_fast_size(n, false, [](auto) { return true; });
+}
+template <typename T>
+static inline int nk_fast_strided_tile(int n) {
+  return nk_with_fast_size(n, 0, [](auto N) {
+    return StridedTile<T, N()>::TILE > StridedTile<T, N(), false, 0>::TILE ? StridedTile<T, N()>::TILE : StridedTile<T, N(), false, 0>::TILE;
+  });
 }
 template <typename T>
 static inline bool nk_fast_strided_ok(int n, int64_t inner) {
@@ -1613,11 +1613,7 @@ static inline bool nk_fast_contig_ok(int h) { return nk_fast_size(h); }
 // lines of 4096 points; NK_TWO_LEVEL=0: never, =2: also 2048 (fp64) and 4096 (fp32).  The two schedules round differently.
 template <typename T>
 static inline bool nk_tl_split(const NkGeom& g, int& n1, int& n2) {
-#ifdef NK_HOST_EMU
-  const int on = nk_env_int("NK_TWO_LEVEL", 1);  // (tests switch it per call)
-#else
-  static const int on = nk_env_int("NK_TWO_LEVEL", 1);
-#endif
+  const int on = nk_knobs().two_level;
   n1 = n2 = 0;
   if (!on || g.ndim != 2) return false;
   if (g.na == 4096 && (sizeof(T) == 8 || on >= 2)) n1 = 64, n2 = 64;

@@ -47,36 +47,24 @@ template <typename T, int N, int PC>
 int nk_twin_launch_strided(const NkPassS& ps, int64_t blocks, const C2<T>* tw, int xmap, hipStream_t st) {
   using ST = StridedTile<T, N, nk_strided_cx<3, PC>(), 3>;
   const NkBatchCtx& bc = *t_batch;
-  auto kb = k2_strided_b<T, N, 3, PC>;
-  static unsigned long long attr_mask = 0;  // per-device attribute
-  if (ST::LDS_TOTAL > 64 * 1024 && nk_first_on_device(attr_mask)) {
-    hipError_t e = hipFuncSetAttribute((const void*)kb, hipFuncAttributeMaxDynamicSharedMemorySize, ST::LDS_TOTAL);
-    if (e != hipSuccess) return nk_set_hip_error(e, "hipFuncSetAttribute(k2_strided_b)");
-  }
   NkFuseArr fa;
   for (int m = 0; m < NK_MAX_BATCH; ++m) fa.f[m] = bc.fuse[m < bc.count ? m : 0];
-  hipLaunchKernelGGL(kb, dim3((unsigned)blocks, (unsigned)bc.count), dim3(ST::THREADS), ST::LDS_TOTAL, st, ps, fa, tw, bc.wa, xmap);
-  return nk_check_launch("k2_strided_b");
+  return nk_launch<k2_strided_b<T, N, 3, PC>>("k2_strided_b", dim3((unsigned)blocks, (unsigned)bc.count), dim3(ST::THREADS), ST::LDS_TOTAL, st,
+                                              ps, fa, tw, bc.wa, xmap);
 }
 
 template <typename T, int NL, bool COUPLES, int EC>
 int nk_twin_launch_final(const NkPassF& pf, int64_t blocks, const C2<T>* tw, int xmap, hipStream_t st) {
   using CT = FinalTile<T, NL, EC, COUPLES ? 2 : 1>;
   const NkBatchCtx& bc = *t_batch;
-  auto kb = k2_final_b<T, NL, COUPLES, EC, 0>;
-  static unsigned long long attr_mask = 0;  // per-device attribute
-  if (CT::LDS_BYTES > 64 * 1024 && nk_first_on_device(attr_mask)) {
-    hipError_t e = hipFuncSetAttribute((const void*)kb, hipFuncAttributeMaxDynamicSharedMemorySize, CT::LDS_BYTES);
-    if (e != hipSuccess) return nk_set_hip_error(e, "hipFuncSetAttribute(k2_final_b)");
-  }
   NkFuseArr fa;
   for (int m = 0; m < NK_MAX_BATCH; ++m) fa.f[m] = bc.final_fuse[m < bc.count ? m : 0];
   // every wavefront owns one slot of a member's energy area: never drop a partial silently
   for (int m = 0; m < bc.count; ++m)
     if (fa.f[m].value_slots > 0 && blocks * ((CT::THREADS + 63) / 64) > fa.f[m].value_slots)
       return nk_set_error(NK_ERR_RUNTIME, "final pass: more wavefronts than reduction slots (nk_value_slot_count)");
-  hipLaunchKernelGGL(kb, dim3((unsigned)blocks, (unsigned)bc.count), dim3(CT::THREADS), CT::LDS_BYTES, st, pf, fa, tw, bc.wa, xmap);
-  return nk_check_launch("k2_final_b");
+  return nk_launch<k2_final_b<T, NL, COUPLES, EC, 0>>("k2_final_b", dim3((unsigned)blocks, (unsigned)bc.count), dim3(CT::THREADS), CT::LDS_BYTES,
+                                                      st, pf, fa, tw, bc.wa, xmap);
 }
 
 // explicit instantiations: exactly the classes of nk_twin_strided / nk_twin_final (nk_fft_batch.h)

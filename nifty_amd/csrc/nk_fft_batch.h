@@ -99,8 +99,7 @@ constexpr bool nk_twin_final() {
 }
 
 static bool nk_batch_class_ok(const NkGeom& g, const nk_fuse& f) {
-  static const int generic = nk_env_int("NK_EC_GENERIC", 0);
-  if (generic || g.na < 512 || g.nl < 512) return false;
+  if (nk_knobs().ec_generic || g.na < 512 || g.nl < 512) return false;
   const bool pro_ok = f.pro == NK_PRO_PLAIN || f.pro == NK_PRO_MUL ||
                       (f.field_octant && !f.io32 && (f.pro == NK_PRO_AMP || f.pro == NK_PRO_AMP_JVP));
   const bool epi_ok = f.epi == NK_EPI_MUL || (f.epi == NK_EPI_LIKELIHOOD && !f.io32) || f.epi == NK_EPI_NONLIN ||

@@ -73,31 +73,22 @@ template <typename T, int NL, int HAND>
 static int nk_launch_final_pair_h(NkPassF pf, const NkFuse& fa, const NkFuse& fb, const C2<T>* tw, const C2<T>* worka,
                                   const C2<T>* workb, hipStream_t st) {
   using CT = FinalTile<T, NL, 2, 2>;
-  static const int pad = nk_env_int("NK_PAIR_PAD_LDS", 0);  // experiment: occupancy of the HAND = 0 launch at the stash's LDS cost
-  const int LDS = (HAND ? PairTile<T, NL>::LDS_HAND : CT::LDS_BYTES) + (HAND ? 0 : pad);
-  auto kern = k2_final2<T, NL, HAND>;
-  static unsigned long long attr_mask = 0;  // per-device attribute
-  if (LDS > 64 * 1024 && nk_first_on_device(attr_mask)) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) return nk_set_hip_error(e, "hipFuncSetAttribute(k2_final2)");
-  }
+  const int LDS = HAND ? PairTile<T, NL>::LDS_HAND : CT::LDS_BYTES + nk_knobs().pair_pad_lds;  // (NK_PAIR_PAD_LDS: experiment, nk_plan.h)
   pf.tiles_per_a = (pf.A > 1 && CT::TILE >= 2) ? (pf.M / 2 + 1 + CT::TILE / 2 - 1) / (CT::TILE / 2) : (pf.M + CT::TILE - 1) / CT::TILE;
   pf.blk0 = 0;
   const int64_t blocks = (int64_t)pf.g.batch * (pf.A / 2 + 1) * pf.tiles_per_a;
   const int64_t waves = blocks * ((CT::THREADS + 63) / 64);
   if ((fa.value_slots > 0 && waves > fa.value_slots) || (fb.value_slots > 0 && waves > fb.value_slots))
     return nk_set_error(NK_ERR_RUNTIME, "final pass: more wavefronts than reduction slots (nk_value_slot_count)");
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(CT::THREADS), LDS, st, pf, fa, fb, tw, worka, workb);
-  return nk_check_launch("k2_final2");
+  return nk_launch<k2_final2<T, NL, HAND>>("k2_final2", dim3((unsigned)blocks), dim3(CT::THREADS), LDS, st, pf, fa, fb, tw, worka, workb);
 }
 
 template <typename T, int NL>
 int nk_launch_final_pair(NkPassF pf, const NkFuse& fa, const NkFuse& fb, const C2<T>* tw, const C2<T>* worka, const C2<T>* workb,
                          hipStream_t st) {
-  static const int hand = nk_env_int("NK_PAIR_HAND", 0);
   // 3-D line couples only (the launcher's caller guarantees a 3-D plan; A > 1 is what makes the bodies pair lines as couples)
   if constexpr (PairTile<T, NL>::HAND_OK) {
-    if (hand && pf.A > 1) {
+    if (nk_knobs().pair_hand && pf.A > 1) {
       if (fa.out == fb.out && fb.accumulate) return nk_launch_final_pair_h<T, NL, 2>(pf, fa, fb, tw, worka, workb, st);
       if (fb.carry1 == fa.out && fb.out != fa.out) return nk_launch_final_pair_h<T, NL, 3>(pf, fa, fb, tw, worka, workb, st);
     }

@@ -44,12 +44,10 @@ static int nk_tl_launch(NkPassS ps, int other, const NkFuse& f, const C2<T>* tw,
     const NkBatchCtx& bc = *t_batch;
     NkFuseArr fa;
     for (int m = 0; m < NK_MAX_BATCH; ++m) fa.f[m] = bc.fuse[m < bc.count ? m : 0];
-    hipLaunchKernelGGL((k2_tl_b<T, N, MODE, PC>), dim3((unsigned)blocks, (unsigned)bc.count), dim3(ST::THREADS), ST::LDS_BYTES, st, ps, fa, tw,
-                       tw_full, bc.wa);
-    return nk_check_launch("k2_tl_b");
+    return nk_launch<k2_tl_b<T, N, MODE, PC>>("k2_tl_b", dim3((unsigned)blocks, (unsigned)bc.count), dim3(ST::THREADS), ST::LDS_BYTES, st, ps, fa,
+                                              tw, tw_full, bc.wa);
   }
-  hipLaunchKernelGGL((k2_tl<T, N, MODE, PC>), dim3((unsigned)blocks), dim3(ST::THREADS), ST::LDS_BYTES, st, ps, f, tw, tw_full, work);
-  return nk_check_launch("k2_tl");
+  return nk_launch<k2_tl<T, N, MODE, PC>>("k2_tl", dim3((unsigned)blocks), dim3(ST::THREADS), ST::LDS_BYTES, st, ps, f, tw, tw_full, work);
 }
 
 // the prologue classes of nk_launch_strided that the fused engine launches on 2-D grids; everything else: run-time class

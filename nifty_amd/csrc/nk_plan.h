@@ -53,6 +53,77 @@ static inline int nk_env_int(const char* name, int dflt) {
   return v ? atoi(v) : dflt;
 }
 
+// ---- the switches of the fast transform path: one record, every default written here and nowhere else ------------------
+// Development / measurement only (tools/README.md, "Environment knobs"); the field initialisers are what bench.py and the
+// tests run.  (The generic planner's NK_TILE_A/B/C, NK_TILE_C2C and NK_THREADS_A/S are not in here: they are passed to
+// nk_pick_strided_tile by NAME, one per pass, and read once at plan creation.)
+#ifndef NK_XMAP_DEFAULT
+#define NK_XMAP_DEFAULT 9
+#endif
+struct NkKnobs {
+  int fast = 1;      // NK_FAST: 0 = generic LDS kernels for every size (the register-resident path off)
+  int pipeline = 2;  // NK_PIPELINE: 1 = contiguous-first pipeline (passes A, B, C, D) instead of the strided-first one
+  // NK_XMAP: XCD-contiguous block order (nk_xcd_contig), a bit mask.  Bit 0: first strided pass, bit 1: every in-place
+  // strided pass, bit 2: final pass, bit 3: the in-place middle-axis pass of the sandwich only (blo > 0: 1.66 -> 1.62 ms at
+  // 1024^3 fp32, while the in-place pass of the six-pass pipeline loses 8 % with it)
+  int xmap = NK_XMAP_DEFAULT;
+  // NK_WORK_BLO, NK_WORK_PAD: the 3-D work array is made of natural [batch][first] slabs whose stride is padded by
+  // NK_WORK_PAD elements -- the in-place pass over the first axis otherwise walks an exact power-of-two stride (nm*nl/2
+  // elements: HBM channel aliasing, 2.9 -> 2.05 ms at 1024^3 fp32).  NK_WORK_BLO=1 selects the transposed slab order
+  // [batch][mid][first][last/2] instead (second pass at stride nl/2, first-pass stores at the big stride): measured slower
+  // in total.
+  int work_blo = 0;
+  int work_pad = 2080;
+  // NK_CONTIG_QUAD: 1 = QUAD workgroups for every launch of the sandwich's contiguous first pass on a 3-D grid, 2 = for the
+  // staged launches of a pipelined sandwich only, 0 = never (nk_contig3_quad).  QUAD cuts the FETCH of the JVP class from
+  // 15.2 to 10.1 GB per launch at 1024^3 fp32 (the octant lines of a[pidx] / da[pidx] are read once per workgroup instead of
+  // once per row); on an otherwise idle GPU the pass takes the same time either way (3.59-3.63 vs 3.60-3.61 ms per launch
+  // over a bench step, identical bits: the extra fetches were served by L2 / Infinity Cache) -- the smaller footprint on
+  // the fabric is what a rank wants while its RCCL exchange runs beside the pass.
+  int contig_quad = 1;
+  int ec_generic = 0;     // NK_EC_GENERIC: 1 = final pass with the run-time epilogue switch instead of the compile-time classes
+  int two_level = 1;      // NK_TWO_LEVEL: two-level first-axis pass of 2-D grids, 0 = never, 2 = more lengths (nk_tl_split, nk_fft2.h)
+  int skip_final = 0;     // NK_SKIP_FINAL: 1 = stop after the strided passes (debugging / timing aid: wrong results)
+  int mid_wg_per_cu = 0;  // NK_MID_WG_PER_CU: > 0 = workgroups per CU of the persistent middle kernel (-DNK_MID_PF builds)
+  int pair_hand = 0;      // NK_PAIR_HAND: 1 = the LDS hand-over variants of k2_final2 (-DNK_PAIR_HAND_BUILD=1 builds, nk_fft_p.hip)
+  int pair_pad_lds = 0;   // NK_PAIR_PAD_LDS: experiment, occupancy of the HAND = 0 launch of k2_final2 at the stash's LDS cost (bytes)
+  int tile_divides = 0;   // NK_TILE_DIVIDES: 1 = strided tiles of the generic planner must divide the slab width (nk_pick_strided_tile)
+};
+static inline NkKnobs nk_read_knobs() {
+  NkKnobs k;
+  k.fast = nk_env_int("NK_FAST", k.fast);
+  k.pipeline = nk_env_int("NK_PIPELINE", k.pipeline);
+  k.xmap = nk_env_int("NK_XMAP", k.xmap);
+  k.work_blo = nk_env_int("NK_WORK_BLO", k.work_blo);
+  k.work_pad = nk_env_int("NK_WORK_PAD", k.work_pad);
+  k.contig_quad = nk_env_int("NK_CONTIG_QUAD", k.contig_quad);
+  k.ec_generic = nk_env_int("NK_EC_GENERIC", k.ec_generic);
+  k.two_level = nk_env_int("NK_TWO_LEVEL", k.two_level);
+  k.skip_final = nk_env_int("NK_SKIP_FINAL", k.skip_final);
+  k.mid_wg_per_cu = nk_env_int("NK_MID_WG_PER_CU", k.mid_wg_per_cu);
+  k.pair_hand = nk_env_int("NK_PAIR_HAND", k.pair_hand);
+  k.pair_pad_lds = nk_env_int("NK_PAIR_PAD_LDS", k.pair_pad_lds);
+  k.tile_divides = nk_env_int("NK_TILE_DIVIDES", k.tile_divides);
+  return k;
+}
+// The library reads the environment ONCE per process, at the first use (`inline`, not `static`: one record for all of its
+// translation units, so a launcher and the plan queries can never disagree).  The host emulation reads it on every call:
+// its tests switch NK_TWO_LEVEL between calls inside one process.
+inline NkKnobs nk_knobs() {
+#ifdef NK_HOST_EMU
+  return nk_read_knobs();
+#else
+  static const NkKnobs k = nk_read_knobs();
+  return k;
+#endif
+}
+// QUAD workgroups or row tiles for a launch of the sandwich's contiguous first pass (classes and lengths that have a QUAD
+// build, Contig3Tile::QUAD_OK)?  nblk > 0: one stage of a pipelined sandwich.
+static inline bool nk_contig3_quad(int64_t nblk, int ndim) {
+  const int quad = nk_knobs().contig_quad;
+  return (quad == 1 || (quad == 2 && nblk > 0)) && ndim == 3;
+}
+
 struct NkHostPlan {
   NkGeom g{};
   int dtype = 1;
@@ -98,7 +169,7 @@ static inline int nk_pick_strided_tile(int n, int64_t inner, size_t csize, const
   // resident workgroups with rows of 8 (768^3: -12 %, profiles/r04_generic_sweep.log)
   size_t budget = 128 * 1024;
   int T = 1;
-  static const int divides = nk_env_int("NK_TILE_DIVIDES", 0);
+  const int divides = nk_knobs().tile_divides;
   auto fits = [&](int t) { return (int64_t)t <= inner && (!divides || inner % t == 0); };
   while (fits(T * 2) && (size_t)n * (T * 2) * csize <= budget && (size_t)(T * 2) * csize <= 256) T *= 2;
   if ((size_t)T * csize < 64) {  // rows shorter than 64 B: all the LDS a workgroup can have

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdio>
+
 #include "../../include/niftyk.h"
 
 int nk_set_error(int code, const char* msg);
@@ -13,7 +15,7 @@ static inline int nk_check_launch(const char* what) {
   return NK_OK;
 }
 
-// Function attributes (dynamic LDS size) are per DEVICE: a launcher keeps one bit per device id in a static mask.
+// Function attributes (dynamic LDS size) are per DEVICE: nk_launch keeps one bit per device id in a static mask.
 // Returns true the first time it is called for the current device (ids >= 64 are set every time).
 static inline bool nk_first_on_device(unsigned long long& mask) {
   int dev = 0;
@@ -23,6 +25,26 @@ static inline bool nk_first_on_device(unsigned long long& mask) {
   mask |= bit;
   return true;
 }
+
+// Every launch of a fast-path transform kernel: KERN<<<grid, block, lds_bytes, st>>>(args...), then the launch check.  A
+// kernel may use more than 64 KiB of dynamic LDS only after opting in: the first launch of THIS instantiation (the helper is
+// templated on the kernel, so the mask is its own) on the current device raises the limit.
+#if defined(__HIPCC__)
+template <auto KERN, typename... Args>
+static inline int nk_launch(const char* name, dim3 grid, dim3 block, int lds_bytes, hipStream_t st, const Args&... args) {
+  static unsigned long long attr_mask = 0;
+  if (lds_bytes > 64 * 1024 && nk_first_on_device(attr_mask)) {
+    hipError_t e = hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+    if (e != hipSuccess) {
+      char what[128];
+      snprintf(what, sizeof(what), "hipFuncSetAttribute(%s)", name);
+      return nk_set_hip_error(e, what);
+    }
+  }
+  hipLaunchKernelGGL(KERN, grid, block, lds_bytes, st, args...);
+  return nk_check_launch(name);
+}
+#endif
 
 // Scratch of the deterministic (ticket-ordered) reductions of nk_vec.hip: block partials + ticket, one set per
 // (device, stream), allocated on first use and kept for the life of the process.  Launches on ONE stream are serialised

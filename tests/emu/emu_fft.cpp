@@ -207,10 +207,9 @@ static void emu3_final(const NkPassF& pf, const nk_fuse& f, const C2<T>* tw, con
 template <typename T, int H>
 static void emu3_contig(const NkPass3& p, const nk_fuse& f, const C2<T>* tw, const C2<T>* twr, C2<T>* work) {
   using CT = Contig3Tile<T, H>;
-  // QUAD launches of the octant classes on 3-D grids: as nk_launch_contig3 (NK_CONTIG_QUAD=0 switches them off there too)
-  const char* qenv = getenv("NK_CONTIG_QUAD");
+  // QUAD launches of the octant classes: the decision of nk_launch_contig3 (nk_contig3_quad)
   if constexpr (CT::QUAD_OK) {
-    if (f.field_octant && p.g.ndim == 3 && (f.pro == NK_PRO_AMP || f.pro == NK_PRO_AMP_JVP) && !(qenv && atoi(qenv) == 0)) {
+    if (f.field_octant && (f.pro == NK_PRO_AMP || f.pro == NK_PRO_AMP_JVP) && nk_contig3_quad(p.nblk, p.g.ndim)) {
       std::vector<T> qplanes(CT::QLDS_BYTES / sizeof(T));
       // the launch grid of nk_launch_contig3: x = the (a8, b8) index inside a batch member, y = the member
       const int64_t batch = p.nlines / ((int64_t)p.g.na * p.g.nm);
@@ -308,48 +307,20 @@ static int emu4_run(int ndim, const int64_t* shape, int dtype, int64_t batch, co
   auto tw_a = conv_tw<T>(hp.tw_a), twr = conv_tw<T>(hp.twr_a), tw_b = conv_tw<T>(hp.tw_b), tw_c = conv_tw<T>(hp.tw_c),
        tw_f = conv_tw<T>(hp.tw_f);
   const int sign = convention == NK_HARTLEY_CANONICAL ? -1 : 1;
-  const NkPipe3 q = nk_pipe3_setup<T>(hp, sign, 2080, scale_first * (f->mul_scalar != 0.0 ? f->mul_scalar : 1.0));
+  const NkPipe3 q = nk_pipe3_setup<T>(hp, sign, NkKnobs{}.work_pad, scale_first * (f->mul_scalar != 0.0 ? f->mul_scalar : 1.0));
   if (!nk_fast_strided_ok<T>(g.na, q.pm.s.inner) || (ndim == 3 && !nk_fast_strided_ok<T>(g.nm, q.rs))) return -100;
-  if (nk_pipe3_work_elems(g, nk_pipe3_colpad<T>(), 2080) * sizeof(C2<T>) > hp.work_bytes) return -101;
+  if (nk_pipe3_work_elems(g, nk_pipe3_colpad<T>(), NkKnobs{}.work_pad) * sizeof(C2<T>) > hp.work_bytes) return -101;
   // poison the work array: every element a later pass reads must have been written by an earlier one
   std::vector<C2<T>> work(hp.work_bytes / sizeof(C2<T>) + 1, C2<T>{(T)NAN, (T)NAN});
   double energy = 0.0;
-  switch (g.h) {
-#define NK_CASE(NN) \
-  case NN:          \
-    emu3_contig<T, NN>(q.p1, *f, tw_a.data(), twr.data(), work.data()); \
-    break;
-    NK_FAST_SIZES(NK_CASE)
-#undef NK_CASE
-  }
+  nk_with_fast_size(g.h, 0, [&](auto N) { emu3_contig<T, N()>(q.p1, *f, tw_a.data(), twr.data(), work.data()); return 0; });
   auto mid_axis = [&]() {
-    switch (g.nm) {
-#define NK_CASE(NN) \
-  case NN:          \
-    emu2_strided<T, NN>(q.s2, 0, *f, tw_b.data(), work.data(), nullptr, &energy); \
-    break;
-      NK_FAST_SIZES(NK_CASE)
-#undef NK_CASE
-    }
+    nk_with_fast_size(g.nm, 0, [&](auto N) { emu2_strided<T, N()>(q.s2, 0, *f, tw_b.data(), work.data(), nullptr, &energy); return 0; });
   };
   if (ndim == 3) mid_axis();
-  switch (g.na) {
-#define NK_CASE(NN) \
-  case NN:          \
-    emu3_mid<T, NN>(q.pm, *f, tw_c.data(), work.data(), cx); \
-    break;
-    NK_FAST_SIZES(NK_CASE)
-#undef NK_CASE
-  }
+  nk_with_fast_size(g.na, 0, [&](auto N) { emu3_mid<T, N()>(q.pm, *f, tw_c.data(), work.data(), cx); return 0; });
   if (ndim == 3) mid_axis();
-  switch (g.nl) {
-#define NK_CASE(NN) \
-  case NN:          \
-    emu3_final<T, NN>(q.pf, *f, tw_f.data(), work.data(), &energy); \
-    break;
-    NK_FAST_SIZES(NK_CASE)
-#undef NK_CASE
-  }
+  nk_with_fast_size(g.nl, 0, [&](auto N) { emu3_final<T, N()>(q.pf, *f, tw_f.data(), work.data(), &energy); return 0; });
   if ((f->epi == NK_EPI_LIKELIHOOD || f->epi == NK_EPI_VJP) && f->value) *f->value += energy;
   return NK_OK;
 }
@@ -375,19 +346,10 @@ static int emu3_run(int ndim, const int64_t* shape, int dtype, int64_t batch, co
   if (!nk_fast_strided_ok<T>(g.na, hp.pc.inner)) return -102;
   double energy = 0.0;
   std::vector<C2<T>> work(hp.work_bytes / sizeof(C2<T>) + 1);
-  NkPipe2 pq = nk_pipe2_setup(hp, convention == NK_HARTLEY_CANONICAL ? -1 : 1, nk_env_int("NK_WORK_BLO", 0),
-                              nk_env_int("NK_WORK_PAD", 2080));
+  NkPipe2 pq = nk_pipe2_setup(hp, convention == NK_HARTLEY_CANONICAL ? -1 : 1, nk_knobs().work_blo, nk_knobs().work_pad);
   NkPassS pb = pq.s1, pc = ndim == 3 ? pq.s0 : pq.s1;
-  if (ndim == 3) {
-    switch (g.nm) {
-#define NK_CASE(NN) \
-  case NN:          \
-    emu2_strided<T, NN>(pb, 3, *f, tw_b.data(), work.data(), nullptr, &energy); \
-    break;
-      NK_FAST_SIZES(NK_CASE)
-#undef NK_CASE
-    }
-  }
+  if (ndim == 3)
+    nk_with_fast_size(g.nm, 0, [&](auto N) { emu2_strided<T, N()>(pb, 3, *f, tw_b.data(), work.data(), nullptr, &energy); return 0; });
   int tl_n1 = 0, tl_n2 = 0;
   if (nk_tl_split<T>(g, tl_n1, tl_n2)) {
     // two-level first-axis pass (nk_fft_t.hip: nk_tl_first_axis): n1-point sub-lines with the prologue, n2-point ones in place
@@ -395,24 +357,11 @@ static int emu3_run(int ndim, const int64_t* shape, int dtype, int64_t batch, co
     emu_tl<T, 64, 4>(pc, tl_n2, *f, tw1.data(), tw_c.data(), work.data());
     if (tl_n2 == 64) emu_tl<T, 64, 5>(pc, tl_n1, *f, tw2.data(), tw_c.data(), work.data());
     else emu_tl<T, 32, 5>(pc, tl_n1, *f, tw2.data(), tw_c.data(), work.data());
-  } else
-  switch (g.na) {
-#define NK_CASE(NN) \
-  case NN:          \
-    emu2_strided<T, NN>(pc, ndim == 3 ? 0 : 3, *f, tw_c.data(), work.data(), nullptr, &energy); \
-    break;
-    NK_FAST_SIZES(NK_CASE)
-#undef NK_CASE
+  } else {
+    nk_with_fast_size(g.na, 0, [&](auto N) { emu2_strided<T, N()>(pc, ndim == 3 ? 0 : 3, *f, tw_c.data(), work.data(), nullptr, &energy); return 0; });
   }
   const NkPassF pf = pq.pf;
-  switch (g.nl) {
-#define NK_CASE(NN) \
-  case NN:          \
-    emu2_final<T, NN>(pf, *f, tw_f.data(), work.data(), &energy); \
-    break;
-    NK_FAST_SIZES(NK_CASE)
-#undef NK_CASE
-  }
+  nk_with_fast_size(g.nl, 0, [&](auto N) { emu2_final<T, N()>(pf, *f, tw_f.data(), work.data(), &energy); return 0; });
   if ((f->epi == NK_EPI_LIKELIHOOD || f->epi == NK_EPI_VJP) && f->value) *f->value += energy;
   return NK_OK;
 }
@@ -437,14 +386,7 @@ static int emu2_run(int ndim, const int64_t* shape, int dtype, int64_t batch, co
   pa.g.sign = convention == NK_HARTLEY_CANONICAL ? -1 : 1;
   double energy = 0.0;
   std::vector<C2<T>> work(hp.work_bytes / sizeof(C2<T>) + 1), scratch(hp.scratch_bytes / sizeof(C2<T>) + 1);
-  switch (g.h) {
-#define NK_CASE(NN) \
-  case NN:          \
-    emu2_contig<T, NN>(pa, ndim == 1, *f, tw_a.data(), twr.data(), work.data(), &energy); \
-    break;
-    NK_FAST_SIZES(NK_CASE)
-#undef NK_CASE
-  }
+  nk_with_fast_size(g.h, 0, [&](auto N) { emu2_contig<T, N()>(pa, ndim == 1, *f, tw_a.data(), twr.data(), work.data(), &energy); return 0; });
   if ((f->epi == NK_EPI_LIKELIHOOD || f->epi == NK_EPI_VJP) && f->value) *f->value += energy;
   return NK_OK;
 }
