@@ -194,6 +194,25 @@ int nk_hartley_sandwich(const nk_plan* plan, const nk_fuse* fuse, double scale_f
  * `out` unwritten in this form; the product build always stores it.) */
 int nk_hartley_sandwich_pair(const nk_plan* plan, const nk_fuse* fuse_a, const nk_fuse* fuse_b, double scale_first,
                              int convention, void* workspace_a, void* workspace_b, void* stream);
+/* A GROUP of 1 .. NK_MAX_GROUP sandwiches that read the same large operand (the sampling solves of one linearisation point
+ * share `xi` and `afield`; the samples of a KL metric share `in`): exactly nk_hartley_sandwich(fuses[0], workspaces[0]), then
+ * fuses[1], ... -- same arithmetic, same reduction-slot order, same bits -- with the contiguous first passes in ONE launch and
+ * the final passes in ONE launch, their workgroups ordered so that the members' workgroups for the same rows run side by side
+ * on one XCD and the later requests for a shared row are served by its L2 (nk_group_order below).  The middle passes stay one
+ * launch set per member.  Requirements: 3-D plan, every member passes the checks of nk_hartley_sandwich, all members select
+ * the same prologue and epilogue class (cg_r set for all or for none), no slab pipelining, and no array one member WRITES
+ * (`in` under cg_r, out, w8, w8max, value, abar without w8, its workspace) overlaps an array another member reads or writes
+ * (NK_ERR_INVALID); read-only operands may be shared freely.  Grouped kernels exist for the AMP_JVP prologue on octant fields
+ * (with or without cg_r) and the VJP epilogue with an octant amplitude field; any other class, and NK_GROUP=0, runs member by
+ * member. */
+#define NK_MAX_GROUP 4
+int nk_hartley_sandwich_group(const nk_plan* plan, const nk_fuse* fuses, int count, double scale_first, int convention,
+                              void* const* workspaces, void* stream);
+/* Block order of a grouped launch (host copy of the kernels' decode, for tests): workgroup `bid` of the grid serves workgroup
+ * *local of member *member, local % 8 == bid % 8; nk_group_grid_size(per, count) workgroups cover `per` workgroups per member
+ * (those with *local >= per leave at once). */
+int nk_group_order(int64_t bid, int count, int64_t* member, int64_t* local);
+int64_t nk_group_grid_size(int64_t per, int count);
 /* complex-to-complex: in/out interleaved (re,im) of the plan dtype; inverse != 0 uses exp(+i..);
  * result is multiplied by `scale` (pass 1/N for numpy-style ifftn).  in == out allowed. */
 int nk_fftn(const nk_plan* plan, const void* in, void* out, int inverse, double scale, void* workspace,

@@ -72,6 +72,9 @@ SIGNATURES = {
     "nk_plan_pipe_ok": (_i, [_vp, _i]),
     "nk_hartley_sandwich": (_i, [_vp, ctypes.POINTER(Fuse), _d, _i, _vp, _vp]),
     "nk_hartley_sandwich_pair": (_i, [_vp, ctypes.POINTER(Fuse), ctypes.POINTER(Fuse), _d, _i, _vp, _vp, _vp]),
+    "nk_hartley_sandwich_group": (_i, [_vp, ctypes.POINTER(Fuse), _i, _d, _i, _vp, _vp]),
+    "nk_group_order": (_i, [_i64, _i, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "nk_group_grid_size": (_i64, [_i64, _i]),
     "nk_fftn": (_i, [_vp, _vp, _vp, _i, _d, _vp, _vp]),
     "nk_profile_enable": (_i, [_i]),
     "nk_profile_collect": (_i, [_vp, _vp]),
@@ -147,6 +150,7 @@ SIGNATURES = {
     "nk_cg_direction_batch": (_i, [_i64, _i, _vp, _vp, _i, _vp, _i, _vp]),
 }
 MAX_BATCH = 8  # NK_MAX_BATCH of include/niftyk.h
+MAX_GROUP = 4  # NK_MAX_GROUP of include/niftyk.h
 
 
 def ptr_array(tensors):

@@ -294,6 +294,17 @@ def hartley_sandwich_pair(plan, fuse_a, fuse_b, scale_first, workspace_b):
             "nk_hartley_sandwich_pair")
 
 
+def hartley_sandwich_group(plan, fuses, scale_first, workspaces):
+    """`len(fuses)` sandwiches that share read-only operands, first and final passes in one launch each
+    (nk_hartley_sandwich_group): same bits as one hartley_sandwich call per member on its own workspace."""
+    if plan.device.index != _current_device():
+        _wrong_device(plan.device.index)
+    arr = (L.Fuse * len(fuses))(*fuses)
+    L.check(L.load().nk_hartley_sandwich_group(plan.handle, arr, len(fuses), float(scale_first), _convention(),
+                                               ctypes.cast(L.ptr_array(workspaces), ctypes.c_void_p), _stream()),
+            "nk_hartley_sandwich_group")
+
+
 def fftn(x, ndim=None, inverse=False, scale=1.0):
     """c2c FFT over the last ``ndim`` axes of a complex tensor (reference ducc_dispatch.fftn / ifftn)."""
     _require_device(x)
@@ -882,7 +893,7 @@ def _runs_on_operand_device(fn):
     return wrapper
 
 
-for _name in ("cplx_rows", "cplx_pointwise", "hartley", "hartley_fused", "hartley_sandwich", "hartley_sandwich_pair", "fftn", "vdot", "vsum", "binary", "axpby",
+for _name in ("cplx_rows", "cplx_pointwise", "hartley", "hartley_fused", "hartley_sandwich", "hartley_sandwich_pair", "hartley_sandwich_group", "fftn", "vdot", "vsum", "binary", "axpby",
               "axpby_sqnorm",
               "pointwise", "gather", "scatter_add", "bin_plan", "bin_sum", "spmv", "spmv_t", "stats", "cumsum"):
     globals()[_name] = _runs_on_operand_device(globals()[_name])

@@ -339,22 +339,7 @@ __global__ void __launch_bounds__((Contig3Tile<T, H>::THREADS)) NK_CONTIG3_ATTR
 // Occupancy the compiler aims at (= its register budget): a row pass lives on the loads it keeps in flight, and with a free
 // hand the compiler trades registers for resident waves (k3_contig_quad<double,256,5>: 88 VGPRs, five waves per SIMD --
 // 0.69 ms; capped at four waves it takes 144 VGPRs and 0.62 ms).  Per field type and prologue class, from measurements.
-#ifndef NK_QUAD_MAXW_F64_5
-#define NK_QUAD_MAXW_F64_5 4
-#endif
-#ifndef NK_QUAD_MAXW_F64_8
-#define NK_QUAD_MAXW_F64_8 8
-#endif
-#ifndef NK_QUAD_MAXW_F32_5
-#define NK_QUAD_MAXW_F32_5 8
-#endif
-#ifndef NK_QUAD_MAXW_F32_8
-#define NK_QUAD_MAXW_F32_8 8
-#endif
-template <typename T, int PC>
-constexpr int nk_quad_max_waves() {
-  return sizeof(T) == 8 ? (PC == 8 ? NK_QUAD_MAXW_F64_8 : NK_QUAD_MAXW_F64_5) : (PC == 8 ? NK_QUAD_MAXW_F32_8 : NK_QUAD_MAXW_F32_5);
-}
+// (the per-class caps NK_QUAD_MAXW_* and nk_quad_max_waves live in nk_fft_batch.h: the grouped twins share them)
 template <typename T, int H, int PC>
 __global__ void __launch_bounds__((Contig3Tile<T, H>::QTHREADS))
     k3_contig_quad(NkPass3 p, NkFuse f, const C2<T>* __restrict__ tw, const C2<T>* __restrict__ twr, C2<T>* __restrict__ work) {
@@ -1257,7 +1242,7 @@ extern "C" int nk_plan_pipe_ok(const nk_plan* P, int chunks) {
 
 template <typename T>
 static int nk_run_sandwich(const nk_plan* P, const NkFuse& f, double scale_first, int convention, void* workspace, hipStream_t st,
-                           bool with_final = true, NkPipe3* q_out = nullptr) {
+                           bool with_final = true, NkPipe3* q_out = nullptr, bool with_first = true) {
   const NkHostPlan& hp = P->hp;
   const int sign = convention == NK_HARTLEY_CANONICAL ? -1 : 1;
   const int work_pad = nk_knobs().work_pad;
@@ -1278,7 +1263,10 @@ static int nk_run_sandwich(const nk_plan* P, const NkFuse& f, double scale_first
                                                "the first axis, and an octant amplitude prologue");
   }
   const int wc = C ? hp.g.na / C : 0;  // slabs per chunk
-  if (C) {
+  if (!with_first) {
+    // (the first pass of this member went out in a grouped launch, nk_group_first)
+    if (C) return nk_set_error(NK_ERR_UNSUPPORTED, "grouped first pass: no slab pipelining");
+  } else if (C) {
     const int Mh = hp.g.nm / 2 + 1;
     for (int j = 0; j < C / 2; ++j) {
       // rows a8 = j wc .. (j+1) wc - 1 (the last stage also a8 = na / 2) and their mirrors: chunks <= j and >= C-1-j of `in`
@@ -1374,13 +1362,185 @@ extern "C" int nk_hartley_sandwich(const nk_plan* P, const nk_fuse* fuse, double
   return nk_run_sandwich<double>(P, *fuse, scale_first, convention, workspace, st);
 }
 
+
+// ---- grouped launches (nk_hartley_sandwich_group; block order and kernels: nk_fft_batch.h, nk_fft_g.hip) --------------------
+extern "C" int nk_group_order(int64_t bid, int count, int64_t* member, int64_t* local) {
+  if (bid < 0 || count < 1 || count > NK_MAX_GROUP || !member || !local)
+    return nk_set_error(NK_ERR_INVALID, "nk_group_order: bid >= 0, 1 <= count <= NK_MAX_GROUP");
+  nk_group_decode(bid, count, *member, *local);
+  return NK_OK;
+}
+extern "C" int64_t nk_group_grid_size(int64_t per, int count) { return nk_group_grid(per, count); }
+
+// do these members' first passes (prologue class 5 or 8) have a grouped QUAD launch on this plan?
+static bool nk_group_first_ok(const nk_plan* P, const nk_fuse* fuses, int count) {
+  const NkGeom& g = P->hp.g;
+  if (!nk_knobs().group || g.ndim != 3 || g.batch != 1 || !nk_contig3_quad(0, 3)) return false;
+  if (!(P->hp.dtype == NK_F32 ? nk_contig3_quad_ok<float>(g.h) : nk_contig3_quad_ok<double>(g.h))) return false;
+  for (int m = 0; m < count; ++m) {
+    const nk_fuse& f = fuses[m];
+    if (!(f.field_octant && f.pro == NK_PRO_AMP_JVP && f.dafield) || f.pipe_chunks || !f.cg_r != !fuses[0].cg_r) return false;
+  }
+  return true;
+}
+static bool nk_group_final_ok(const nk_plan* P, const nk_fuse* fuses, int count) {
+  const NkGeom& g = P->hp.g;
+  if (!nk_knobs().group || g.ndim != 3 || g.batch != 1 || nk_knobs().skip_final) return false;
+  for (int m = 0; m < count; ++m)
+    if (!(fuses[m].epi == NK_EPI_VJP && fuses[m].afield && fuses[m].field_octant) || fuses[m].pipe_chunks) return false;
+  return true;
+}
+
+template <typename T>
+static int nk_group_first(const nk_plan* P, const NkPass3& p1, const nk_fuse* fuses, int count, void* const* ws, hipStream_t st) {
+  NkGroupFuse fa;
+  NkGroupWork wa;
+  for (int m = 0; m < NK_MAX_GROUP; ++m) {
+    fa.f[m] = fuses[m < count ? m : 0];
+    wa.work[m] = ws[m < count ? m : 0];
+  }
+  const bool c8 = fuses[0].cg_r != nullptr;
+  ProfScope ps(st, 5, c8 ? 4 : fuses[0].pro, fuses[0].epi, count);  // `count` launches of the single kernel's key
+  const C2<T>* tw = (const C2<T>*)P->d_tw_a;
+  const C2<T>* twr = (const C2<T>*)P->d_twr_a;
+  return nk_dispatch_fast(P->hp.g.h, "no fast contiguous pass for this length", [&](auto N) {
+    return c8 ? nk_group_launch_contig3<T, N(), 8>(p1, fa, wa, count, tw, twr, st) : nk_group_launch_contig3<T, N(), 5>(p1, fa, wa, count, tw, twr, st);
+  });
+}
+
+// the members' reduction slots are set up member by member (nk_final_with_slots, as the pair launch does), innermost the launch
+template <typename T>
+static int nk_group_final(const nk_plan* P, const NkPassF& pf, const nk_fuse* fuses, int count, void* const* ws, hipStream_t st, int m,
+                          NkGroupFuse& fa) {
+  const NkHostPlan& hp = P->hp;
+  if (m < count)
+    return nk_final_with_slots(hp, ws[m], fuses[m], st, [&](const NkFuse& f2) {
+      fa.f[m] = f2;
+      return nk_group_final<T>(P, pf, fuses, count, ws, st, m + 1, fa);
+    });
+  NkGroupWork wa;
+  for (int k = 0; k < NK_MAX_GROUP; ++k) {
+    if (k >= count) fa.f[k] = fa.f[0];
+    wa.work[k] = ws[k < count ? k : 0];
+  }
+  return nk_dispatch_fast(hp.g.nl, "no fast final pass for this length",
+                          [&](auto N) { return nk_group_launch_final<T, N()>(pf, fa, wa, count, (const C2<T>*)P->d_tw_f, st); });
+}
+
+template <typename T>
+static int nk_run_sandwich_group(const nk_plan* P, const nk_fuse* fuses, int count, double scale_first, int convention, void* const* ws,
+                                 hipStream_t st) {
+  const bool gfirst = nk_group_first_ok(P, fuses, count), gfinal = nk_group_final_ok(P, fuses, count);
+  if (count == 1 || (!gfirst && !gfinal)) {
+    for (int m = 0; m < count; ++m) {
+      const int rc = nk_run_sandwich<T>(P, fuses[m], scale_first, convention, ws[m], st);
+      if (rc != NK_OK) return rc;
+    }
+    return NK_OK;
+  }
+  const NkHostPlan& hp = P->hp;
+  const NkPipe3 q = nk_pipe3_setup<T>(hp, convention == NK_HARTLEY_CANONICAL ? -1 : 1, nk_knobs().work_pad, 1.0);
+  if (nk_pipe3_work_elems(hp.g, nk_pipe3_colpad<T>(), nk_knobs().work_pad) * sizeof(C2<T>) > hp.work_bytes)
+    return nk_set_error(NK_ERR_RUNTIME, "nk_hartley_sandwich: plan workspace too small");
+  int rc;
+  if (gfirst) {
+    rc = nk_group_first<T>(P, q.p1, fuses, count, ws, st);
+    if (rc != NK_OK) return rc;
+  }
+  for (int m = 0; m < count; ++m) {  // the middle passes share nothing: one launch set per member, unchanged
+    rc = nk_run_sandwich<T>(P, fuses[m], scale_first, convention, ws[m], st, !gfinal, nullptr, !gfirst);
+    if (rc != NK_OK) return rc;
+  }
+  if (!gfinal) return NK_OK;
+  NkGroupFuse fa;
+  ProfScope ps(st, 3, fuses[0].pro, fuses[0].epi, count);
+  return nk_group_final<T>(P, q.pf, fuses, count, ws, st, 0, fa);
+}
+
+// [lo, hi) of an array a member touches; two members may share what both only read
+struct NkSpan {
+  const char* lo;
+  const char* hi;
+  bool written;
+};
+static int nk_member_spans(const nk_plan* P, const nk_fuse& f, void* workspace, NkSpan* out) {
+  const NkGeom& g = P->hp.g;
+  const size_t ts = P->hp.dtype == NK_F32 ? 4 : 8;
+  const size_t full = (size_t)g.batch * g.na * g.nm * g.nl * ts;
+  const size_t oct_n = (size_t)(g.na / 2 + 1) * (g.nm / 2 + 1) * (g.nl / 2 + 1);
+  int n = 0;
+  auto add = [&](const void* p, size_t bytes, bool written) {
+    if (p) out[n++] = NkSpan{(const char*)p, (const char*)p + bytes, written};
+  };
+  add(f.in, full, f.cg_r != nullptr);
+  add(f.in2, full, false);
+  add(f.cg_r, full, false);
+  add(f.xi, full, false);
+  add(f.addend, full, false);
+  add(f.carry1, full, false);
+  add(f.carry2, full, false);
+  add(f.mul, full, false);
+  add(f.afield, f.field_octant ? oct_n * ts : full, false);
+  add(f.dafield, f.field_octant ? oct_n * ts : full, false);
+  add(f.out, full, true);
+  add(f.w8, (size_t)g.batch * oct_n * sizeof(double), true);
+  add(f.w8max, sizeof(double), true);
+  add(f.value, sizeof(double), true);
+  if (!f.w8 && f.abar) add(f.abar, (size_t)((f.abar_copies > 1 ? f.abar_copies - 1 : 0) * f.abar_stride + 1) * sizeof(double), true);
+  add(workspace, nk_plan_workspace_bytes(P), true);
+  return n;
+}
+
+extern "C" int nk_hartley_sandwich_group(const nk_plan* P, const nk_fuse* fuses, int count, double scale_first, int convention,
+                                         void* const* workspaces, void* stream) {
+  if (!P || !fuses || !workspaces || count < 1 || count > NK_MAX_GROUP)
+    return nk_set_error(NK_ERR_INVALID, "nk_hartley_sandwich_group: bad argument (1 <= count <= NK_MAX_GROUP)");
+  if (P->hp.g.ndim != 3) return nk_set_error(NK_ERR_UNSUPPORTED, "nk_hartley_sandwich_group: 3-D plans only");
+  NkSpan spans[NK_MAX_GROUP][20];
+  int nspan[NK_MAX_GROUP];
+  for (int m = 0; m < count; ++m) {
+    const int rc = nk_sandwich_check(P, fuses + m, convention, workspaces[m]);
+    if (rc != NK_OK) return rc;
+    if (fuses[m].pipe_chunks) return nk_set_error(NK_ERR_UNSUPPORTED, "nk_hartley_sandwich_group: no slab pipelining");
+    if (!nk_same_class(fuses[0], fuses[m]) || !fuses[0].cg_r != !fuses[m].cg_r)
+      return nk_set_error(NK_ERR_INVALID, "nk_hartley_sandwich_group: the members select different kernel classes");
+    nspan[m] = nk_member_spans(P, fuses[m], workspaces[m], spans[m]);
+    // an array one member writes must not overlap an array another member reads or writes: the grouped passes run the
+    // members side by side (shared READ-ONLY operands are the point of the exercise)
+    for (int k = 0; k < m; ++k)
+      for (int i = 0; i < nspan[m]; ++i)
+        for (int j = 0; j < nspan[k]; ++j) {
+          const NkSpan &a = spans[m][i], &b = spans[k][j];
+          if ((a.written || b.written) && a.lo < b.hi && b.lo < a.hi)
+            return nk_set_error(NK_ERR_INVALID, "nk_hartley_sandwich_group: an array one member writes overlaps an array of another "
+                                                 "member (in under cg_r, out, w8, w8max, value, abar and the workspace are written)");
+        }
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (P->hp.dtype == NK_F32) return nk_run_sandwich_group<float>(P, fuses, count, scale_first, convention, workspaces, st);
+  return nk_run_sandwich_group<double>(P, fuses, count, scale_first, convention, workspaces, st);
+}
+
 template <typename T>
 static int nk_run_sandwich_pair(const nk_plan* P, const NkFuse& fa, const NkFuse& fb, double scale_first, int convention,
                                 void* wsa, void* wsb, hipStream_t st) {
   NkPipe3 q;
-  int rc = nk_run_sandwich<T>(P, fa, scale_first, convention, wsa, st, false, &q);
+  int rc;
+  // the two first passes as a group of two (nk_fft_g.hip) when neither carries the pending direction update: they only read
+  // their operands -- the samples of a KL metric share the direction -- and write their own work arrays
+  const nk_fuse pair[2] = {fa, fb};
+  void* const wsp[2] = {wsa, wsb};
+  const bool gfirst = !fa.cg_r && !fb.cg_r && nk_same_class(fa, fb) && nk_group_first_ok(P, pair, 2);
+  if (gfirst) {
+    const NkPipe3 q0 = nk_pipe3_setup<T>(P->hp, convention == NK_HARTLEY_CANONICAL ? -1 : 1, nk_knobs().work_pad, 1.0);
+    if (nk_pipe3_work_elems(P->hp.g, nk_pipe3_colpad<T>(), nk_knobs().work_pad) * sizeof(C2<T>) > P->hp.work_bytes)
+      return nk_set_error(NK_ERR_RUNTIME, "nk_hartley_sandwich: plan workspace too small");
+    rc = nk_group_first<T>(P, q0.p1, pair, 2, wsp, st);
+    if (rc != NK_OK) return rc;
+  }
+  rc = nk_run_sandwich<T>(P, fa, scale_first, convention, wsa, st, false, &q, !gfirst);
   if (rc != NK_OK) return rc;
-  rc = nk_run_sandwich<T>(P, fb, scale_first, convention, wsb, st, false, nullptr);
+  rc = nk_run_sandwich<T>(P, fb, scale_first, convention, wsb, st, false, nullptr, !gfirst);
   if (rc != NK_OK) return rc;
   const NkHostPlan& hp = P->hp;
   ProfScope ps(st, 9, fa.pro, fa.epi);  // its own profile key: one launch, two final passes

@@ -125,3 +125,57 @@ int nk_tl_first_axis(const NkPassS& s1, int n1, int n2, const NkFuse& f, const C
 template <typename T, int NL>
 int nk_launch_final_pair(NkPassF pf, const NkFuse& fa, const NkFuse& fb, const C2<T>* tw, const C2<T>* worka, const C2<T>* workb,
                          hipStream_t st);
+
+// ---- grouped launches of the sandwich's first and final pass (nk_hartley_sandwich_group, include/niftyk.h) ------------------
+// Up to NK_MAX_GROUP members that read the same N-sized operand (the sampling solves of one linearisation point share xi
+// and a[pidx]; the samples of a KL metric share the direction d) go through ONE launch whose workgroups are ordered so that
+// the members' workgroups for the same rows are neighbours in dispatch order AND sit on one XCD: the hardware deals
+// workgroup b to XCD b % 8 (observed, not a contract -- speed only), so with
+//     g = bid / (8 count), w = bid % (8 count), x = w % 8, member = w / 8, local = 8 g + x
+// member m's workgroup `local` lands on XCD local % 8 exactly as in its single launch, next to the other members'
+// workgroups of the same `local`: the second request for a shared row is served by that XCD's L2 instead of the fabric.
+// The grid covers ceil(per / 8) full groups; workgroups with local >= per leave at once.  Kernel bodies, registers and LDS
+// are those of the single launches (same bits).
+NK_HD void nk_group_decode(int64_t bid, int count, int64_t& member, int64_t& local) {
+  const int64_t span = 8 * (int64_t)count;
+  const int64_t g = bid / span, w = bid % span;
+  member = w / 8;
+  local = 8 * g + w % 8;
+}
+static inline int64_t nk_group_grid(int64_t per, int count) { return (per + 7) / 8 * 8 * count; }
+struct NkGroupFuse {
+  NkFuse f[NK_MAX_GROUP];
+};
+struct NkGroupWork {
+  void* work[NK_MAX_GROUP];
+};
+
+// Occupancy caps of the QUAD first pass per field type and prologue class (see k3_contig_quad in nk_fft.hip)
+#ifndef NK_QUAD_MAXW_F64_5
+#define NK_QUAD_MAXW_F64_5 4
+#endif
+#ifndef NK_QUAD_MAXW_F64_8
+#define NK_QUAD_MAXW_F64_8 8
+#endif
+#ifndef NK_QUAD_MAXW_F32_5
+#define NK_QUAD_MAXW_F32_5 8
+#endif
+#ifndef NK_QUAD_MAXW_F32_8
+#define NK_QUAD_MAXW_F32_8 8
+#endif
+template <typename T, int PC>
+constexpr int nk_quad_max_waves() {
+  return sizeof(T) == 8 ? (PC == 8 ? NK_QUAD_MAXW_F64_8 : NK_QUAD_MAXW_F64_5) : (PC == 8 ? NK_QUAD_MAXW_F32_8 : NK_QUAD_MAXW_F32_5);
+}
+
+// the grouped launchers: defined and explicitly instantiated in nk_fft_g.hip (first pass: prologue classes 5 and 8 as QUAD
+// workgroups; final pass: the VJP epilogue on line couples with row-mirror pairing)
+template <typename T, int H, int PC>
+int nk_group_launch_contig3(const NkPass3& p3, const NkGroupFuse& fa, const NkGroupWork& wa, int count, const C2<T>* tw, const C2<T>* twr,
+                            hipStream_t st);
+template <typename T, int NL>
+int nk_group_launch_final(NkPassF pf, const NkGroupFuse& fa, const NkGroupWork& wa, int count, const C2<T>* tw, hipStream_t st);
+template <typename T, int H>
+constexpr bool nk_group_quad_ok() {
+  return Contig3Tile<T, H>::QUAD_OK;
+}

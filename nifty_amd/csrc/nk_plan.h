@@ -87,6 +87,7 @@ struct NkKnobs {
   int mid_wg_per_cu = 0;  // NK_MID_WG_PER_CU: > 0 = workgroups per CU of the persistent middle kernel (-DNK_MID_PF builds)
   int pair_hand = 0;      // NK_PAIR_HAND: 1 = the LDS hand-over variants of k2_final2 (-DNK_PAIR_HAND_BUILD=1 builds, nk_fft_p.hip)
   int pair_pad_lds = 0;   // NK_PAIR_PAD_LDS: experiment, occupancy of the HAND = 0 launch of k2_final2 at the stash's LDS cost (bytes)
+  int group = 1;          // NK_GROUP: 0 = nk_hartley_sandwich_group / _pair launch every member's first and final pass on its own
   int tile_divides = 0;   // NK_TILE_DIVIDES: 1 = strided tiles of the generic planner must divide the slab width (nk_pick_strided_tile)
 };
 static inline NkKnobs nk_read_knobs() {
@@ -103,6 +104,7 @@ static inline NkKnobs nk_read_knobs() {
   k.mid_wg_per_cu = nk_env_int("NK_MID_WG_PER_CU", k.mid_wg_per_cu);
   k.pair_hand = nk_env_int("NK_PAIR_HAND", k.pair_hand);
   k.pair_pad_lds = nk_env_int("NK_PAIR_PAD_LDS", k.pair_pad_lds);
+  k.group = nk_env_int("NK_GROUP", k.group);
   k.tile_divides = nk_env_int("NK_TILE_DIVIDES", k.tile_divides);
   return k;
 }

@@ -1106,6 +1106,80 @@ class FusedModel:
                     "nk_octant_scatter_k2")
             self._finish_metric(lp, d, out, is_first, ident, dest)
 
+    def group_ready(self):
+        """True when the metric applications of several solves at one linearisation point can go out as grouped launches
+        (lh_metric_group; NK_GROUP=0: never)."""
+        return bool(self.pair_ready() and self.fused_direction and os.environ.get("NK_GROUP", "1") != "0"
+                    and os.environ.get("NK_DA_GATHER", "0") != "1")
+
+    def _group_buffers(self, count):
+        """`count` sets of the per-application scratch arrays: the model's own, the pair's second set (_pair_buffers), then
+        further ones allocated on first use."""
+        own = dict(damp=self.damp, dafield=self.dafield, w8=self.w8, w8max=self.w8max, workspace=self.plan.workspace)
+        sets = [own, self._pair_buffers()] if count > 1 else [own]
+        more = self.__dict__.setdefault("_group_more", [])
+        while len(sets) + len(more) < count:
+            more.append(dict(damp=torch.empty_like(self.damp), dafield=torch.empty_like(self.dafield),
+                             w8=torch.empty_like(self.w8), w8max=torch.zeros_like(self.w8max),
+                             workspace=torch.empty_like(self.plan.workspace)))
+        return (sets + more)[:count]
+
+    def release_group_buffers(self):
+        """Hand the scratch sets beyond the pair's back to the allocator (the sampling phase is over: the KL that follows
+        holds one position per sample and needs the room)."""
+        self.__dict__.pop("_group_more", None)
+
+    def lh_metric_group(self, lp, jobs):
+        """[J^T M J d + identity * d  (or + factor * vector)] for up to L.MAX_GROUP directions at ONE linearisation point --
+        the sampling solves of an MGVI iteration -- as one nk_hartley_sandwich_group call: the first passes, which all read
+        lp.x.xi and a[pidx], share a launch, and so do the final passes.  jobs: dicts with `d` and optionally `identity`,
+        `addend` = (vector, factor), `dot_out`, `cg_direction` (all or none) as in lh_metric_accumulate, `lp` = a linearisation
+        point of its own (samples of a KL that share the direction instead); per job the kernels,
+        the arithmetic and the bits are those of lh_metric_accumulate(lp, d, out, 1.0, True, ...).  Returns the outputs."""
+        lib = L.load()
+        bufs = self._group_buffers(len(jobs))
+        fuses, outs, adds = [], [], []
+        points = [job.get("lp", lp) for job in jobs]
+        for job, buf, lp in zip(jobs, bufs, points):
+            d = job["d"]
+            avec, afac = (d, job.get("identity", 0.0)) if job.get("addend") is None else job["addend"]
+            out = LatentVec(torch.empty_like(d.xi), None)
+            L.check(lib.nk_amp_jvp(self.nb, self.geo.data_ptr(), self.hyp.data_ptr(), lp.x.small.data_ptr(), lp.state.data_ptr(),
+                                   d.small.data_ptr(), buf["damp"].data_ptr(), B._stream()), "nk_amp_jvp")
+            self._amp_field(buf["damp"], out=buf["dafield"])
+            f = self._fuse()
+            f.pro, f.in_, f.in2 = L.PRO_AMP_JVP, d.xi.data_ptr(), lp.x.xi.data_ptr()
+            f.pidx, f.amp, f.damp = self.pidx.data_ptr(), lp.amp.data_ptr(), buf["damp"].data_ptr()
+            f.afield, f.dafield = B.ptr(lp.afield), buf["dafield"].data_ptr()
+            if job.get("cg_direction") is not None:
+                f.cg_r, f.cg_scal = job["cg_direction"][0].xi.data_ptr(), job["cg_direction"][1].scal.data_ptr()
+            f.mul, f.mul_scalar = B.ptr(lp.mid), lp.mid_scalar
+            f.epi, f.out, f.scale = L.EPI_VJP, out.xi.data_ptr(), self.h_dvol
+            f.xi = lp.x.xi.data_ptr()
+            f.addend, f.addend_scale, f.accumulate = B.ptr(avec.xi if afac else None), afac, 0
+            if job.get("dot_out") is not None:
+                if not afac:
+                    raise ValueError("dot_out needs an addend and the register-resident transform pipeline")
+                f.value = job["dot_out"].data_ptr()
+            f.abar, f.w8 = self.abar.data_ptr(), buf["w8"].data_ptr()
+            if self.scatter_fixed_point:
+                f.w8max = buf["w8max"].data_ptr()
+            fuses.append(f)
+            outs.append(out)
+            adds.append((avec, afac))
+        B.hartley_sandwich_group(self.plan, fuses, self.h_dvol, [buf["workspace"] for buf in bufs])
+        shp = (ctypes.c_int64 * len(self.shape))(*self.shape)
+        for job, buf, out, (avec, afac), lp in zip(jobs, bufs, outs, adds, points):
+            self._count("transforms", 2)
+            L.check(lib.nk_octant_scatter_k2(len(self.shape), shp, buf["w8"].data_ptr(), self.pidx.data_ptr(), self.bin_k2.data_ptr(),
+                                             self.nb, self.scatter_scratch.data_ptr(), self.abar.data_ptr(),
+                                             buf["w8max"].data_ptr() if self.scatter_fixed_point else 0, B._stream()),
+                    "nk_octant_scatter_k2")
+            if job.get("cg_direction") is not None:
+                job["cg_direction"][1].roll()
+            self._finish_metric(lp, avec, out, True, afac, _Dest(out.xi, accumulate=False))
+        return outs
+
     def _finish_metric(self, lp, d, out, first, identity, dest=None):
         self._amp_vjp(lp)
         if dest is not None:
@@ -1916,7 +1990,20 @@ def draw_samples(model, position, n_samples, mirror_samples, controller_factory,
     lanes = _sampling_lanes(model, local_pairs)
     # the linear solves of the iteration advance together: as batched launches (nifty_amd/batched.py) or on stream lanes
     in_batch = local_pairs >= 2 and batched.ready(model)
-    if lanes is None and not in_batch:
+    # ... and on large 3-D grids in lock-step with grouped launches of the metric's first and final pass (_solve_grouped)
+    grouped = (lanes is None and not in_batch and local_pairs >= 2 and geo_minimizer is None and model.group_ready()
+               and model.N > int(os.environ.get("NK_LANE_MAX_POINTS", str(1 << 25))))
+    if grouped:
+        if want_ahead:
+            ahead = _HostDrawAhead(model, drawn_seeds)
+        try:
+            drawn = plan.run_together(
+                lambda seed: _draw_sources(model, linearisation(), seed, device_rng, ahead.take(seed) if ahead else None),
+                lambda jobs: _solve_grouped(model, linearisation(), jobs, controller_factory), finish)
+        finally:
+            if ahead is not None:
+                ahead.close()
+    elif lanes is None and not in_batch:
         if want_ahead:
             ahead = _HostDrawAhead(model, drawn_seeds)
         try:
@@ -2026,11 +2113,90 @@ def _sampling_lanes(model, pairs):
     return model.lanes(min(want, pairs))
 
 
-def _draw_sources(model, lp, seed, device_rng):
+def _draw_sources(model, lp, seed, device_rng, ahead=None):
     """The random inputs of one linear sample (prior draw s, data-space noise pulled back: nj), in the sample's stream."""
     if device_rng is not None:
         device_rng.manual_seed(int(seed.generate_state(1, np.uint64)[0] >> np.uint64(1)))
-    return model.draw_prior(device_rng), model.draw_lh_noise(lp, device_rng)
+    return model.draw_prior(device_rng, ahead=ahead), model.draw_lh_noise(lp, device_rng)
+
+
+class _Ticket:
+    """One metric application a solve has asked for and not yet received (ConjugateGradient._inplace_steps, `apply`)."""
+
+    __slots__ = ("job", "result")
+
+    def __init__(self, job):
+        self.job, self.result = job, None
+
+
+class _GroupedMetric:
+    """(J^T M J + 1) at one linearisation point for several solves that advance in lock-step: `submit` queues an application,
+    `flush` runs everything queued as grouped launches (FusedModel.lh_metric_group) -- applications with and without the
+    pending direction update are different kernel classes and go out as groups of their own."""
+
+    fused_dot = fused_direction = True
+
+    def __init__(self, model, lp, size):
+        self._model, self._lp, self._size, self._queue = model, lp, size, []
+
+    def __call__(self, v, dot_out=None, cg_direction=None):
+        return self._model.metric(self._lp, v, dot_out=dot_out, cg_direction=cg_direction)
+
+    def submit(self, v, dot_out=None, cg_direction=None):
+        ticket = _Ticket(dict(d=v, identity=1.0, dot_out=dot_out, cg_direction=cg_direction))
+        self._queue.append(ticket)
+        return ticket
+
+    def flush(self):
+        queue, self._queue = self._queue, []
+        for with_direction in (False, True):
+            part = [t for t in queue if (t.job["cg_direction"] is not None) == with_direction]
+            for k in range(0, len(part), self._size):
+                chunk = part[k:k + self._size]
+                for ticket, out in zip(chunk, self._model.lh_metric_group(self._lp, [t.job for t in chunk])):
+                    ticket.result = out
+
+
+def _solve_grouped(model, lp, jobs, controller_factory):
+    """FusedModel.draw_mgvi_sample for the solves of one linearisation point in lock-step, NK_GROUP_SOLVES (default 4, at most
+    L.MAX_GROUP) at a time: every solve is ConjugateGradient._inplace_steps on its own vectors, scalars and controller --
+    the single solve's arithmetic and bits --, only the metric applications of one round go out together.  A solve that
+    stops leaves the group, the others go on.  `jobs` is emptied on the way: the noise draws nj are dead once b and the start
+    residual exist, and four solves side by side hold four times the CG vectors of one."""
+    import copy
+
+    size = max(1, min(L.MAX_GROUP, int(os.environ.get("NK_GROUP_SOLVES", str(L.MAX_GROUP)))))
+    pairs = []
+    for w0 in range(0, len(jobs), size):
+        wave = jobs[w0:w0 + size]
+        bs = [s + nj for s, nj in wave]
+        g0s = model.lh_metric_group(lp, [dict(d=s, addend=(nj, -1.0)) for s, nj in wave])  # J^T M J s - nj
+        starts = [s for s, _ in wave]
+        jobs[w0:w0 + size] = [None] * len(wave)
+        del wave
+        op = _GroupedMetric(model, lp, size)
+        runs, controllers = [], []
+        for s, b, g0 in zip(starts, bs, g0s):
+            energy = QuadraticEnergy(s, op, b, _grad=g0)
+            energy.consumable = True  # s and g0 belong to this solve: the CG may update them in place
+            controller = controller_factory()
+            if any(controller is other for other in controllers):
+                controller = copy.deepcopy(controller)  # (one controller object handed out for every solve: see _solve_on_lanes)
+            controllers.append(controller)
+            runs.append(ConjugateGradient(None)._inplace_steps(energy, controller))
+        results, active = [None] * len(runs), list(range(len(runs)))
+        while active:
+            for k in list(active):
+                try:
+                    next(runs[k])
+                except StopIteration as done:
+                    results[k] = done.value
+                    active.remove(k)
+            op.flush()
+        pairs += [(b, energy.position) for b, (energy, _) in zip(bs, results)]
+        del runs, results, starts, g0s, op
+    model.release_group_buffers()
+    return pairs
 
 
 def _solve_on_lanes(model, lanes, lp, jobs, controller_factory):

@@ -566,6 +566,17 @@ class ConjugateGradient(Minimizer):
         # (either shortcut without the other: a KL metric that sums its samples pairwise has no place for the dot)
         fused_dir = bool(getattr(A, "fused_direction", False)) and hasattr(ws, "direction_small")
 
+        def apply(v, **kw):
+            """A(v, **kw).  An operator with `submit` (engine._GroupedMetric: solves at one linearisation point whose
+            applications go out as ONE grouped launch set) takes the request, the generator yields the ticket, and whoever
+            drives the solves applies the operators of all of them before resuming any: `ticket.result` is A(v, **kw)."""
+            submit = getattr(A, "submit", None)
+            if submit is None:
+                return A(v, **kw)
+            ticket = submit(v, **kw)
+            yield ticket
+            return ticket.result
+
         def device_iteration(with_direction):
             """All device work of one iteration up to the fused update: [d <- beta d + r;] q = A d; d.q; x, r update."""
             extra = {}
@@ -576,10 +587,10 @@ class ConjugateGradient(Minimizer):
                 ws.direction(d, r)
             if fused_dot:
                 # the operator's last epilogue takes d.q (xi part) while it writes q: one BLAS-1 pass less
-                q = A(d, dot_out=ws.curv_slot(), **extra)
+                q = yield from apply(d, dot_out=ws.curv_slot(), **extra)
                 ws.curv_small(d, q)
             else:
-                q = A(d, **extra)
+                q = yield from apply(d, **extra)
                 ws.curv(d, q)
             if track_energy:
                 ws.update_dr(x, r, d, q)
@@ -601,7 +612,7 @@ class ConjugateGradient(Minimizer):
         iteration = 0
         while True:
             iteration += 1
-            device_iteration(iteration > 1 and not direction_done)
+            yield from device_iteration(iteration > 1 and not direction_done)
             direction_done = False
             counters.add("cg_iterations")
             since_reset += 1
@@ -611,7 +622,7 @@ class ConjugateGradient(Minimizer):
             # exactly this case): the iterate is final, nobody reads that residual, and the refresh is a whole metric
             # application (1 of 22 per sampling solve)
             if since_reset >= self._nreset and not _forced_stop(controller):
-                Ax = A(x)
+                Ax = yield from apply(x)
                 r = Ax - b if b is not None else Ax
                 ws.refresh(x, r, b)
                 since_reset = 0

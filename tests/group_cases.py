@@ -1,0 +1,194 @@
+"""Shared by tests/test_grouped_passes_gpu.py and tests/test_grouped_sampling_gpu.py: the cases, run in the test process and --
+`python -m tests.group_cases passes|sampling` -- in a child process, which prints one JSON line of SHA-256 digests.  The library
+reads NK_GROUP once per process, so `NK_GROUP=0` against the default can only be held against each other across processes."""
+import hashlib
+import json
+import os
+import sys
+
+import torch
+
+PASS_SHAPES = [((64, 64, 128), torch.float64), ((64, 128, 128), torch.float32)]
+
+
+def digest(t):
+    if isinstance(t, torch.Tensor):
+        return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
+    return repr(t)
+
+
+def pass_setup(shape, dtype):
+    """Model with data, five linearisation points, directions / residuals for four members (seeded: the same in every process)."""
+    from nifty_amd import random
+    from nifty_amd.engine import FusedModel
+
+    model = FusedModel(shape, offset_mean=2.0, likelihood="gaussian", icov=100.0, dtype=dtype, device="cuda:0")
+    random.push_sseq_from_seed(11)
+    try:
+        truth = model.draw_prior()
+        model.set_data(model.signal(truth), 100.0)
+        xs = [0.1 * model.draw_prior() for _ in range(5)]
+        ds = [model.draw_prior() for _ in range(4)]
+        rs = [model.draw_prior() for _ in range(4)]
+    finally:
+        random.pop_sseq()
+    return model, xs, ds, rs
+
+
+def _clone(v):
+    from nifty_amd.engine import LatentVec
+
+    return LatentVec(v.xi.clone(), v.small.clone())
+
+
+def _cg_ws(model, m):
+    """A CG workspace in mid-solve: gamma_prev, gamma (beta = gamma / gamma_prev differs per member)."""
+    from nifty_amd.engine import CgWorkspace
+
+    ws = CgWorkspace(torch.device("cuda:0"))
+    ws.scal[0] = 2.0 + m
+    ws.scal[2] = 1.0 + 0.25 * m
+    return ws
+
+
+def class8_jobs(model, ds, rs, count):
+    """Members sharing in2 / xi / afield (one linearisation point) with their own d (rewritten: cg_r), r, workspace scalars,
+    identity addend and curvature dot."""
+    jobs, keep = [], []
+    for m in range(count):
+        d, ws = _clone(ds[m]), _cg_ws(model, m)
+        ws.direction_small(d, rs[m])
+        dot = torch.zeros(1, dtype=torch.float64, device="cuda:0")
+        jobs.append(dict(d=d, identity=1.0, dot_out=dot, cg_direction=(rs[m], ws)))
+        keep.append((d, ws, dot))
+    return jobs, keep
+
+
+def class8_single(model, lp, ds, rs, count):
+    out = {}
+    for m in range(count):
+        d = _clone(ds[m])
+        ws = _cg_ws(model, m)
+        ws.direction_small(d, rs[m])
+        dot = torch.zeros(1, dtype=torch.float64, device="cuda:0")
+        q = model.metric(lp, d, dot_out=dot, cg_direction=(rs[m], ws))
+        out.update({f"out{m}": q.xi, f"small{m}": q.small, f"in{m}": d.xi, f"dot{m}": dot.clone(), f"scal{m}": ws.scal.clone(),
+                    f"w8_{m}": model.w8.clone(), f"w8max{m}": model.w8max.clone()})
+    return out
+
+
+def class8_group(model, lp, ds, rs, count):
+    jobs, keep = class8_jobs(model, ds, rs, count)
+    qs = model.lh_metric_group(lp, jobs)
+    bufs = model._group_buffers(count)
+    out = {}
+    for m, (q, (d, ws, dot), buf) in enumerate(zip(qs, keep, bufs)):
+        out.update({f"out{m}": q.xi, f"small{m}": q.small, f"in{m}": d.xi, f"dot{m}": dot.clone(), f"scal{m}": ws.scal.clone(),
+                    f"w8_{m}": buf["w8"].clone(), f"w8max{m}": buf["w8max"].clone()})
+    return out
+
+
+def class5_single(model, lps, d, count):
+    """Members sharing `in` (one direction) at different linearisation points."""
+    out = {}
+    for m in range(count):
+        q = model.lh_metric(lps[m], d, minus=lps[m].x)
+        out.update({f"out{m}": q.xi, f"small{m}": q.small, f"w8_{m}": model.w8.clone(), f"w8max{m}": model.w8max.clone()})
+    return out
+
+
+def class5_group(model, lps, d, count):
+    qs = model.lh_metric_group(lps[0], [dict(d=d, addend=(lps[m].x, -1.0), lp=lps[m]) for m in range(count)])
+    bufs = model._group_buffers(count)
+    out = {}
+    for m, (q, buf) in enumerate(zip(qs, bufs)):
+        out.update({f"out{m}": q.xi, f"small{m}": q.small, f"w8_{m}": buf["w8"].clone(), f"w8max{m}": buf["w8max"].clone()})
+    return out
+
+
+def kl_metric(model, xs, d):
+    from nifty_amd.engine import FusedKL
+
+    kl = FusedKL(model, xs[0], [x - xs[0] for x in xs], [False] * 5)
+    q = kl.apply_metric(d)
+    return {"kl_xi": q.xi, "kl_small": q.small}
+
+
+def passes_digests():
+    """Everything the grouped entry points produce, by name (the child process under NK_GROUP=0 and the test under the default)."""
+    out = {}
+    for shape, dtype in PASS_SHAPES:
+        model, xs, ds, rs = pass_setup(shape, dtype)
+        lps = [model.linearize(x) for x in xs]
+        tag = "x".join(map(str, shape))
+        for count in (2, 4):
+            for k, v in class8_group(model, lps[0], ds, rs, count).items():
+                out[f"{tag}/c8/{count}/{k}"] = digest(v)
+            for k, v in class5_group(model, lps, ds[0], count).items():
+                out[f"{tag}/c5/{count}/{k}"] = digest(v)
+        for k, v in kl_metric(model, xs, ds[0]).items():
+            out[f"{tag}/{k}"] = digest(v)
+    return out
+
+
+SAMPLING_CASES = {  # name: (mirrored pairs, absolute energy tolerance of the sampling controller, iteration limit, environment)
+    "pairs2": (2, 1e-30, 6, {}),
+    "pairs4": (4, 1e-30, 6, {}),
+    "staggered4": (4, 1e-30, 12, {}),  # solves stop at different iterations: solve k's controller ends it after 12 - 2 k
+    "two_by_two": (4, 1e-30, 6, {"NK_GROUP_SOLVES": "2"}),
+    "refresh": (2, 1e-30, 23, {}),  # past the residual refresh of iteration 20 (an application without direction update)
+}
+
+
+def sampling_case(name):
+    """One mgvi_iteration on (64, 64, 128) fp32 Gaussian through the large-grid path: digests of everything it produces."""
+    from nifty_amd import minimization as M
+    from nifty_amd import random
+    from nifty_amd.engine import FusedModel, mgvi_iteration
+
+    pairs, tol, limit, env = SAMPLING_CASES[name]
+    old = {k: os.environ.get(k) for k in list(env) + ["NK_LANE_MAX_POINTS"]}
+    os.environ.update(env)
+    os.environ["NK_LANE_MAX_POINTS"] = "0"
+    try:
+        model = FusedModel((64, 64, 128), offset_mean=2.0, likelihood="gaussian", icov=100.0, dtype=torch.float32, device="cuda:0")
+        random.push_sseq_from_seed(5)
+        try:
+            truth = model.draw_prior()
+            model.set_data(model.signal(truth), 100.0)
+            mean = 0.1 * model.draw_prior()
+            before = M.counters.get("cg_iterations")
+            stops = []
+
+            def factory():
+                # (a loose energy tolerance stops these statistically alike solves at the SAME iteration; what the case is
+                # about -- solves leaving the group one by one -- is made certain by the controllers' own limits instead)
+                own = limit - 2 * (len(stops) % 4) if name == "staggered4" else limit
+                c = M.AbsDeltaEnergyController(tol, convergence_level=1, iteration_limit=own)
+                stops.append(c)
+                return c
+
+            mini = M.NewtonCG(M.AbsDeltaEnergyController(0.5, convergence_level=2, iteration_limit=2), max_cg_iterations=4)
+            new_mean, kl = mgvi_iteration(model, mean, pairs, factory, mini)
+        finally:
+            random.pop_sseq()
+        out = {"mean_xi": digest(new_mean.xi), "mean_small": digest(new_mean.small), "kl": repr(float(kl.value)),
+               "counters": repr(sorted(model.counters.items())), "cg_iterations": M.counters.get("cg_iterations") - before,
+               "solve_lengths": repr([getattr(c, "_itcount", None) for c in stops])}
+        for i, r in enumerate(kl.residuals if hasattr(kl, "residuals") else kl._res):
+            out[f"res{i}_xi"], out[f"res{i}_small"] = digest(r.xi), digest(r.small)
+        return out
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def sampling_digests():
+    return {name: sampling_case(name) for name in SAMPLING_CASES}
+
+
+if __name__ == "__main__":
+    print(json.dumps(passes_digests() if sys.argv[1] == "passes" else sampling_digests()))
