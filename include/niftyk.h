@@ -168,6 +168,10 @@ size_t nk_plan_workspace_bytes(const nk_plan* plan);
 int nk_hartley(const nk_plan* plan, const void* in, void* out, double scale, int convention, void* workspace,
                void* stream);
 int nk_hartley_fused(const nk_plan* plan, const nk_fuse* fuse, int convention, void* workspace, void* stream);
+/* which kernels nk_hartley / nk_hartley_fused launch on this plan:
+ * route[0]: 0 = one-kernel 1-D, 1 = contiguous-first (passes A, B, C, D), 2 = strided-first;
+ * route[1..3]: family of the last- / middle- / first-axis pass: 0 generic LDS kernel, 1 register-resident, 2 two-level; -1 no such axis */
+int nk_plan_route(const nk_plan* plan, int route[4]);
 /* 1 if nk_hartley_sandwich on this plan accepts nk_fuse.pipe_chunks == chunks (slab pipelining, see nk_fuse) */
 int nk_plan_pipe_ok(const nk_plan* plan, int chunks);
 /* Hartley SANDWICH  H D H  of a metric application  J^T M J  (LikelihoodEnergyOperator.get_metric_at,

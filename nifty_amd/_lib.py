@@ -68,6 +68,7 @@ SIGNATURES = {
     "nk_plan_workspace_bytes": (_sz, [_vp]),
     "nk_hartley": (_i, [_vp, _vp, _vp, _d, _i, _vp, _vp]),
     "nk_hartley_fused": (_i, [_vp, ctypes.POINTER(Fuse), _i, _vp, _vp]),
+    "nk_plan_route": (_i, [_vp, ctypes.POINTER(_i)]),
     "nk_plan_sandwich": (_i, [_vp]),
     "nk_plan_pipe_ok": (_i, [_vp, _i]),
     "nk_hartley_sandwich": (_i, [_vp, ctypes.POINTER(Fuse), _d, _i, _vp, _vp]),

@@ -714,15 +714,7 @@ extern "C" int nk_plan_destroy(nk_plan* P) {
   return NK_OK;
 }
 
-static bool nk_plan_uses_pipeline2(const nk_plan* P) {
-  const NkHostPlan& hp = P->hp;
-  const bool f32 = hp.dtype == NK_F32;
-  if (!nk_knobs().fast || nk_knobs().pipeline != 2 || hp.g.ndim < 2 || !nk_fast_size(hp.g.nl)) return false;
-  const bool first_ok = f32 ? nk_fast_strided_ok<float>(hp.g.na, hp.pc.inner) : nk_fast_strided_ok<double>(hp.g.na, hp.pc.inner);
-  const bool mid_ok = hp.g.ndim == 2 || (f32 ? nk_fast_strided_ok<float>(hp.g.nm, hp.pb.inner)
-                                             : nk_fast_strided_ok<double>(hp.g.nm, hp.pb.inner));
-  return first_ok && mid_ok;
-}
+static bool nk_plan_uses_pipeline2(const nk_plan* P) { return nk_route(P->hp).pipe == 2; }
 
 // energy / curvature sums of the final pass: ONE slot per wavefront at the end of the workspace, zeroed before the
 // launch, then folded in a fixed order (k_fold_slots_a: 256 workgroups over contiguous ranges; k_fold_slots_b: their
@@ -880,6 +872,13 @@ static int nk_final_with_slots(const NkHostPlan& hp, void* workspace, const NkFu
 
 extern "C" int nk_plan_octant_vjp(const nk_plan* P) { return P && nk_plan_uses_pipeline2(P) ? 1 : 0; }
 
+extern "C" int nk_plan_route(const nk_plan* P, int route[4]) {
+  if (!P || !route) return nk_set_error(NK_ERR_INVALID, "nk_plan_route: null argument");
+  const NkRoute r = nk_route(P->hp);
+  route[0] = r.pipe, route[1] = r.last, route[2] = r.mid, route[3] = r.first;
+  return NK_OK;
+}
+
 extern "C" size_t nk_plan_workspace_bytes(const nk_plan* P) {
   if (!P) return 0;
   // [work | scratch], scratch aligned to 256 B
@@ -899,7 +898,7 @@ static int nk_run_hartley(const nk_plan* P, const NkFuse& f, int convention, voi
   const C2<T>* twr = (const C2<T>*)P->d_twr_a;
   const int64_t blocks_a = (pa.nlines + pa.tl.tile - 1) / pa.tl.tile;
   if (blocks_a > 0x7fffffffLL) return nk_set_error(NK_ERR_UNSUPPORTED, "too many lines for one launch");
-  const bool fast = nk_knobs().fast != 0;
+  const NkRoute route = nk_route_t<T>(hp);  // the kernel family of every pass (nk_fft2.h; nk_plan_route reports it)
   // Energy / curvature sums of the kernels below (everything but the strided-first pipeline, which brings its own slot
   // handling): one slot per WAVEFRONT in the workspace's slot area, folded in a fixed order afterwards -- bit-reproducible
   // like the fast path (round 3; until then one fp64 atomic per workgroup).  Without a workspace (1-D calls may omit it) or
@@ -928,7 +927,7 @@ static int nk_run_hartley(const nk_plan* P, const NkFuse& f, int convention, voi
   };
   if (hp.g.ndim == 1) {
     ProfScope ps(st, 0, f.pro, f.epi);
-    if (fast && nk_fast_contig_ok(hp.g.h))
+    if (route.last == 1)
       return nk_dispatch_contig<T, true>(hp.g.h, pa, f, tw_a, twr, (C2<T>*)nullptr, st);
     if (slots_on) {
       hipError_t e = hipMemsetAsync(vslots, 0, (size_t)slot_cap * sizeof(double), st);
@@ -946,8 +945,7 @@ static int nk_run_hartley(const nk_plan* P, const NkFuse& f, int convention, voi
   int rc;
   // ---- strided-first pipeline (default when every axis has a specialised kernel): strided c2c passes on the
   //      real array viewed as complex pairs, then ONE contiguous final pass per line pair (k, -k)
-  if (fast && nk_knobs().pipeline == 2 && nk_fast_size(hp.g.nl) && nk_fast_strided_ok<T>(hp.g.na, hp.pc.inner) &&
-      (hp.g.ndim == 2 || nk_fast_strided_ok<T>(hp.g.nm, hp.pb.inner))) {
+  if (route.pipe == 2) {
     // 3-D work array: natural [batch][first] slabs with a padded stride (NK_WORK_PAD, NK_WORK_BLO: nk_plan.h)
     NkPipe2 q = nk_pipe2_setup(hp, pa.g.sign, nk_knobs().work_blo, nk_knobs().work_pad);
     // per-thread address parts are 32-bit: (threads per line) * (row stride) must stay below 2^31 elements
@@ -967,8 +965,8 @@ static int nk_run_hartley(const nk_plan* P, const NkFuse& f, int convention, voi
       rc = nk_dispatch_strided<T, 0>(hp.g.na, q.s0, f, (const C2<T>*)P->d_tw_c, work, scratch, st);
     } else {
       ProfScope ps(st, 1, f.pro, f.epi);  // (the two launches of a two-level pass count as ONE first-axis pass)
-      int n1, n2;
-      if (nk_tl_split<T>(hp.g, n1, n2))
+      int n1, n2;  // route.first == 2 IS nk_tl_split's answer (nk_route_t asks it); the second call only fetches the factors
+      if (route.first == 2 && nk_tl_split<T>(hp.g, n1, n2))
         rc = nk_tl_first_axis<T>(q.s1, n1, n2, f, (const C2<T>*)P->d_tw_t64, (const C2<T>*)(n2 == 64 ? P->d_tw_t64 : P->d_tw_t32),
                                  (const C2<T>*)P->d_tw_c, work, st);
       else
@@ -984,7 +982,7 @@ static int nk_run_hartley(const nk_plan* P, const NkFuse& f, int convention, voi
   }
   {
     ProfScope ps(st, 1, f.pro, f.epi);
-    if (fast && nk_fast_contig_ok(hp.g.h)) {
+    if (route.last == 1) {
       rc = nk_dispatch_contig<T, false>(hp.g.h, pa, f, tw_a, twr, work, st);
     } else {
       hipLaunchKernelGGL(k_passA<T>, dim3((unsigned)blocks_a), dim3(nk_gen_threads<T>(hp.threads_a)), hp.lds_a, st, pa, f, tw_a, twr, work);
@@ -997,7 +995,7 @@ static int nk_run_hartley(const nk_plan* P, const NkFuse& f, int convention, voi
   if (hp.g.ndim == 3) {
     const int64_t blocks_b = hp.pb.outer * hp.pb.tiles_per_slab;
     ProfScope ps(st, 2, f.pro, f.epi);
-    if (fast && nk_fast_strided_ok<T>(hp.g.nm, hp.pb.inner)) {
+    if (route.mid == 1) {
       rc = nk_dispatch_strided<T, 0>(hp.g.nm, hp.pb, f, (const C2<T>*)P->d_tw_b, work, scratch, st);
     } else {
       hipLaunchKernelGGL(k_passB<T>, dim3((unsigned)blocks_b), dim3(nk_gen_threads<T>(hp.threads_b)), hp.lds_b, st, hp.pb,

@@ -1620,6 +1620,30 @@ static inline bool nk_tl_split(const NkGeom& g, int& n1, int& n2) {
   else if (g.na == 2048 && sizeof(T) == 8 && on >= 2) n1 = 64, n2 = 32;
   return n1 > 0;
 }
+// Which kernels a Hartley transform of this plan launches: THE decision of nk_run_hartley, also what nk_plan_route,
+// nk_plan_octant_vjp and the host emulation report.  pipe: 0 = one-kernel 1-D, 1 = contiguous-first (passes A, B, C, D),
+// 2 = strided-first; last / mid / first: family of that axis' pass, 0 = generic LDS kernel, 1 = register-resident,
+// 2 = two-level (nk_tl_split), -1 = the plan has no such axis.
+struct NkRoute {
+  int pipe, last, mid, first;
+};
+template <typename T>
+static inline NkRoute nk_route_t(const NkHostPlan& hp) {
+  const NkGeom& g = hp.g;
+  const NkKnobs k = nk_knobs();
+  const bool fast = k.fast != 0;
+  if (g.ndim == 1) return NkRoute{0, fast && nk_fast_contig_ok(g.h) ? 1 : 0, -1, -1};
+  const bool mid_ok = g.ndim == 3 && fast && nk_fast_strided_ok<T>(g.nm, hp.pb.inner);
+  if (fast && k.pipeline == 2 && nk_fast_size(g.nl) && nk_fast_strided_ok<T>(g.na, hp.pc.inner) && (g.ndim == 2 || mid_ok)) {
+    int n1, n2;
+    return NkRoute{2, 1, g.ndim == 3 ? 1 : -1, nk_tl_split<T>(g, n1, n2) ? 2 : 1};
+  }
+  // contiguous-first: pass C over the first axis is always the generic kernel
+  return NkRoute{1, fast && nk_fast_contig_ok(g.h) ? 1 : 0, g.ndim == 3 ? (mid_ok ? 1 : 0) : -1, 0};
+}
+static inline NkRoute nk_route(const NkHostPlan& hp) {
+  return hp.dtype == NK_F32 ? nk_route_t<float>(hp) : nk_route_t<double>(hp);
+}
 #define NK_WORK_PAD_MAX 8192  // elements; the plan's workspace reserves this much per slab
 #include "nk_fft3.h"
 struct NkPipe2 {

@@ -29,6 +29,14 @@ static void run_stages(C2<T>* lds, int nthr, const NkLinePlan& lp, const NkTile&
   }
 }
 
+// the register-resident bodies (defined below) that a contiguous-first plan mixes with the generic kernels
+template <typename T, int H>
+static void emu2_contig(NkPassA p, bool is_1d, const nk_fuse& f, const C2<T>* tw, const C2<T>* twr, C2<T>* work, double* energy);
+template <typename T, int N>
+static void emu2_strided(NkPassS p, int mode, const nk_fuse& f, const C2<T>* tw, C2<T>* work, C2<T>* scratch, double* energy);
+
+// generic kernels; on a contiguous-first plan (nk_route: pipe == 1) the passes the library runs register-resident --
+// k2_contig<T, H, false> for pass A, k2_strided<T, N, 0> for pass B -- run their bodies here as well, on the same work array
 template <typename T>
 static int emu_run(int ndim, const int64_t* shape, int dtype, int64_t batch, const nk_fuse* f, int convention) {
   NkHostPlan hp;
@@ -41,8 +49,13 @@ static int emu_run(int ndim, const int64_t* shape, int dtype, int64_t batch, con
   double energy = 0.0;
   std::vector<C2<T>> lds(hp.lds_a / sizeof(C2<T>) + 16);
   const int64_t blocks_a = (pa.nlines + pa.tl.tile - 1) / pa.tl.tile;
-  std::vector<C2<T>> work(hp.work_bytes / sizeof(C2<T>) + 1), scratch(hp.scratch_bytes / sizeof(C2<T>) + 1);
-  for (int64_t blk = 0; blk < blocks_a; ++blk) {
+  // poisoned: every element a later pass reads must have been written by an earlier one
+  std::vector<C2<T>> work(hp.work_bytes / sizeof(C2<T>) + 1, C2<T>{(T)NAN, (T)NAN}), scratch(hp.scratch_bytes / sizeof(C2<T>) + 1, C2<T>{(T)NAN, (T)NAN});
+  const NkRoute route = nk_route_t<T>(hp);
+  const bool hybrid = route.pipe == 1;
+  if (hybrid && route.last == 1)
+    nk_with_fast_size(hp.g.h, 0, [&](auto N) { emu2_contig<T, N()>(pa, false, *f, tw_a.data(), twr.data(), work.data(), &energy); return 0; });
+  else for (int64_t blk = 0; blk < blocks_a; ++blk) {
     const int nthr = hp.threads_a;
     for (int tid = 0; tid < nthr; ++tid) nk_passA_load<T>(pa, *f, blk, tid, nthr, lds.data());
     run_stages<T>(lds.data(), nthr, pa.lp, pa.tl, tw_a.data());
@@ -51,7 +64,9 @@ static int emu_run(int ndim, const int64_t* shape, int dtype, int64_t batch, con
       else nk_passA_store<T>(pa, blk, tid, nthr, lds.data(), twr.data(), work.data());
     }
   }
-  if (ndim == 3) {
+  if (ndim == 3 && hybrid && route.mid == 1) {
+    nk_with_fast_size(hp.g.nm, 0, [&](auto N) { emu2_strided<T, N()>(hp.pb, 0, *f, tw_b.data(), work.data(), scratch.data(), &energy); return 0; });
+  } else if (ndim == 3) {
     lds.assign(hp.lds_b / sizeof(C2<T>) + 16, C2<T>{0, 0});
     const int64_t blocks = hp.pb.outer * hp.pb.tiles_per_slab;
     for (int64_t blk = 0; blk < blocks; ++blk) {
@@ -412,5 +427,7 @@ extern "C" int emu_plan_info(int ndim, const int64_t* shape, int dtype, int64_t 
   info[3] = hp.pb.tl.tile; info[4] = hp.threads_b; info[5] = (int64_t)hp.lds_b;
   info[6] = hp.pc.tl.tile; info[7] = hp.threads_c; info[8] = (int64_t)hp.lds_c;
   info[9] = (int64_t)hp.work_bytes; info[10] = (int64_t)hp.scratch_bytes;
+  const NkRoute r = nk_route(hp);  // what nk_plan_route reports
+  info[11] = r.pipe; info[12] = r.last; info[13] = r.mid; info[14] = r.first;
   return NK_OK;
 }

@@ -41,11 +41,37 @@ def fast_fn(shape):
     return "emu2_hartley_fused" if len(shape) == 1 else "emu3_hartley_fused"
 
 
+# contiguous-first plans that mix kernel families (one power-of-two axis beside a mixed-radix one): emu_hartley_fused takes
+# the library's route -- register-resident pass A / pass B where nk_run_hartley launches them, generic kernels for the rest.
+# (pipe, last, mid, first) as nk_plan_route reports it; a pair = (fp64, fp32) where the dtypes differ
+HYBRID_ROUTES = [((30, 128), (1, 1, -1, 0)), ((64, 8192), (1, 1, -1, 0)), ((6, 10, 128), (1, 1, 0, 0)),
+                 ((6, 64, 128), (1, 1, 1, 0)), ((6, 64, 96), (1, 0, 1, 0)),
+                 ((6, 64, 48), ((1, 0, 1, 0), (1, 0, 0, 0)))]  # rows of 24 columns: whole fp64 tiles only
+
+
+def plan_route(shape, dtype, batch=1):
+    info = (ctypes.c_int64 * 16)()
+    shp = (ctypes.c_int64 * len(shape))(*shape)
+    assert lib().emu_plan_info(len(shape), shp, 0 if dtype == np.float32 else 1, ctypes.c_int64(batch), info) == 0
+    return tuple(info[11:15])
+
+
+@pytest.mark.parametrize("shape,route", HYBRID_ROUTES + [((2,), (0, 0, -1, -1)), ((128,), (0, 1, -1, -1)), ((10, 12), (1, 0, -1, 0)),
+                                                         ((9, 25, 28), (1, 0, 0, 0)), ((64, 128), (2, 1, -1, 1)),
+                                                         ((4096, 64), ((2, 1, -1, 2), (2, 1, -1, 1))),
+                                                         ((64, 64, 64), (2, 1, 1, 1))])
+def test_plan_route_of_the_emulation(shape, route):
+    """emu_plan_info reports nk_route, the decision nk_run_hartley branches on (nk_plan_route on the device)."""
+    r64, r32 = route if isinstance(route[0], tuple) else (route, route)
+    assert plan_route(shape, np.float64) == r64
+    assert plan_route(shape, np.float32) == r32
+
+
 @pytest.mark.parametrize("shape", [(2,), (8,), (64,), (1024,), (2, 2), (4, 16), (32, 8), (64, 64), (2, 2, 2), (8, 4, 16),
                                    (16, 16, 16), (2, 32, 4),
                                    # mixed radix 2/3/5/7 (generic kernels; reference test_fft_operator.py:58-103 sizes)
                                    (6,), (10,), (12,), (30,), (210,), (98,), (500,), (3, 4), (6, 10), (15, 14), (50, 18),
-                                   (5, 7, 12), (10, 6, 12), (9, 25, 28)])
+                                   (5, 7, 12), (10, 6, 12), (9, 25, 28)] + [s for s, _ in HYBRID_ROUTES])
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 def test_hartley_emulation(shape, dtype):
     rng = np.random.default_rng(0)
@@ -82,6 +108,7 @@ FUSED_SHAPES = [((64,), "emu_hartley_fused"), ((16, 8), "emu_hartley_fused"), ((
                 ((64, 64, 1024), "emu3_hartley_fused"),  # last axis 1024 in fp64: the smallest final-pass tile
                 ((2048, 64), "emu3_hartley_fused"), ((4096, 128), "emu3_hartley_fused"),  # two-level first-axis pass (64 x 32, 64 x 64)
                 ((64, 4096), "emu3_hartley_fused")]  # 2-D VJP final pass on single line pairs (nk_final_single_2d: 4096 fp64)
+FUSED_SHAPES += [(s, "emu_hartley_fused") for s, _ in HYBRID_ROUTES]  # hybrid contiguous-first routes
 
 
 @pytest.mark.parametrize("shape,fn", FUSED_SHAPES)
