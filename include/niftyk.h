@@ -221,6 +221,14 @@ int64_t nk_group_grid_size(int64_t per, int count);
  * result is multiplied by `scale` (pass 1/N for numpy-style ifftn).  in == out allowed. */
 int nk_fftn(const nk_plan* plan, const void* in, void* out, int inverse, double scale, void* workspace,
             void* stream);
+/* 1 if nk_fftn serves this plan.  Its contiguous pass keeps a line of the FULL last axis in LDS (nl + nl/16 + 1 complex
+ * values in 144 KiB), the real transforms a line of half of it, so nk_plan_create accepts last axes on which nk_fftn returns
+ * NK_ERR_UNSUPPORTED (complex128: 7-smooth even lengths from 8674 on).  The array seam asks this before it calls nk_fftn. */
+int nk_plan_c2c_ok(const nk_plan* plan);
+/* bytes of dynamic LDS of the launches of nk_fftn on this plan: lds[0] the contiguous pass (tile * (nl + nl/16 + 1) complex),
+ * lds[1] / lds[2] the strided passes of the middle / first axis (n * tile complex; 0 = no such pass, or nk_plan_c2c_ok == 0).
+ * For tests that need a shape on one side of the 64 KiB opt-in of nk_plan_create, like nk_plan_route for the real routes. */
+int nk_plan_c2c_lds(const nk_plan* plan, int64_t lds[3]);
 
 /* live profiling for bench.py: when enabled every transform pass kernel launch is bracketed by HIP events on
  * its launch stream; nk_profile_collect synchronises and returns summed milliseconds and launch counts in

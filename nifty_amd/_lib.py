@@ -77,6 +77,8 @@ SIGNATURES = {
     "nk_group_order": (_i, [_i64, _i, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "nk_group_grid_size": (_i64, [_i64, _i]),
     "nk_fftn": (_i, [_vp, _vp, _vp, _i, _d, _vp, _vp]),
+    "nk_plan_c2c_ok": (_i, [_vp]),
+    "nk_plan_c2c_lds": (_i, [_vp, ctypes.POINTER(_i64)]),
     "nk_profile_enable": (_i, [_i]),
     "nk_profile_collect": (_i, [_vp, _vp]),
     "nk_vdot": (_i, [_i64, _vp, _vp, _i, _vp, _i, _vp]),

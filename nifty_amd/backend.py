@@ -111,19 +111,38 @@ def get_plan(shape, dtype, batch=1, device=None):
 _unsupported = set()
 
 
-def plan_supported(shape, dtype, batch=1, device=None):
+C2C_LINE_BYTES = 144 * 1024  # k_c2c_contig keeps one padded line of the FULL last axis in LDS (nk_plan_create)
+
+
+def c2c_line_fits(n, dtype):
+    """The host form of nk_plan_c2c_ok: nl + nl/16 + 1 complex values of the plan's precision in 144 KiB.  The real
+    transforms hold a line of half the last axis, so a plan can exist and still refuse the complex transform."""
+    n = int(n)
+    return (n + n // 16 + 1) * (8 if dtype == torch.float32 else 16) <= C2C_LINE_BYTES
+
+
+def plan_supported(shape, dtype, batch=1, device=None, complex=False):
     """True when the native planner takes this transform (prime factors <= 7, even last axis, line-length limits);
-    otherwise the array seam runs the chirp-z composition below and the fused nodes step aside for the generic graph."""
+    otherwise the array seam runs the chirp-z composition below and the fused nodes step aside for the generic graph.
+    complex: the question is about nk_fftn (c2c_line_fits, decided before any plan is made; nk_plan_c2c_ok of the plan)."""
+    if complex and not c2c_line_fits(shape[-1], dtype):
+        return False
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     key = (tuple(int(s) for s in shape), dtype, int(batch), device.index)
     if key in _unsupported:
         return False
     try:
-        get_plan(shape, dtype, batch, device)
+        plan = get_plan(shape, dtype, batch, device)
     except NotImplementedError:
         _unsupported.add(key)
         return False
-    return True
+    return not complex or bool(L.load().nk_plan_c2c_ok(plan.handle))
+
+
+def _c2c_supported(shape, dtype, batch, device):
+    """what the seam asks before it calls nk_fftn: the line rule on the host first -- a refused length creates no plan --,
+    then the planner"""
+    return c2c_line_fits(shape[-1], dtype) and plan_supported(shape, dtype, batch, device)
 
 
 # ---- any-length fallback (Bluestein / chirp-z), composed from the native power-of-two c2c kernel -------------------
@@ -150,6 +169,8 @@ def _chirp(n, cdt, inverse, device):
         b[m - n + 1:] = w.conj()[1:].flip(0)
         w, b = w.to(cdt).to(device), b.to(cdt).to(device)
         rdt = torch.float32 if cdt == torch.complex64 else torch.float64
+        if not c2c_line_fits(m, rdt):
+            raise NotImplementedError(f"axis of length {n} is too long for the chirp-z fallback")
         get_plan((m,), rdt, 1, device)  # native power-of-two transform or NotImplementedError -- never the fallback again
         ent = _chirps[key] = (m, w, fftn(b, ndim=1))
     return ent
@@ -208,7 +229,7 @@ def _fft_last_axis_any(z, inverse, real_in=False, hartley=0, scale=1.0):
     cdt = torch.complex64 if rdt == torch.float32 else torch.complex128
     batch = z.numel() // max(1, n)
     m = 1 << max(2, (2 * n - 2).bit_length())
-    native = n == 1 or z.numel() == 0 or plan_supported((n,), rdt, batch, z.device)
+    native = n == 1 or z.numel() == 0 or _c2c_supported((n,), rdt, batch, z.device)
     if (not native and m * (8 if rdt == torch.float32 else 16) <= BLUESTEIN_LDS_BYTES and os.environ.get("NK_BLUESTEIN", "1") != "0"):
         # ONE launch: the padded rows stay in LDS through both transforms of the convolution (nk_bluestein_rows)
         w, bhat_br, tw = _bluestein_tables(n, m, cdt, inverse, z.device)
@@ -217,6 +238,11 @@ def _fft_last_axis_any(z, inverse, real_in=False, hartley=0, scale=1.0):
                                            float(scale) if hartley else 1.0, 1 if real_in else 0, int(hartley),
                                            0 if rdt == torch.float32 else 1, _stream()), "nk_bluestein_rows")
         return out
+    # check BEFORE anything is launched or built: an unsupported m must end here, not re-enter this fallback (the cap and the
+    # line rule are host arithmetic: a refused m makes no plan either)
+    if not native and (m > _CHIRP_MAX or not _c2c_supported((m,), rdt, batch, z.device)
+                       or not _c2c_supported((m,), rdt, 1, z.device)):
+        raise NotImplementedError(f"axis of length {n} is too long for the chirp-z fallback")
     if real_in:
         z = cplx_rows(z, None, n, n, 1)
     if n == 1 or z.numel() == 0:
@@ -224,9 +250,6 @@ def _fft_last_axis_any(z, inverse, real_in=False, hartley=0, scale=1.0):
     elif native:
         res = fftn(z, ndim=1, inverse=inverse)
     else:
-        # check BEFORE anything of length m is built: an unsupported m must end here, not re-enter this fallback
-        if m > _CHIRP_MAX or not plan_supported((m,), rdt, batch, z.device) or not plan_supported((m,), rdt, 1, z.device):
-            raise NotImplementedError(f"axis of length {n} is too long for the chirp-z fallback")
         m, w, fb = _chirp(n, z.dtype, inverse, z.device)
         a = cplx_rows(z, w, n, m, 0)                       # x[k] w[k], zero-padded to m
         p = cplx_rows(fftn(a, ndim=1), fb, m, m, 0)        # times the transformed chirp
@@ -315,7 +338,7 @@ def fftn(x, ndim=None, inverse=False, scale=1.0):
     shape = x.shape[x.dim() - ndim:]
     batch = x.numel() // max(1, int(torch.Size(shape).numel()))
     rdt = torch.float32 if x.dtype == torch.complex64 else torch.float64
-    if not plan_supported(shape, rdt, batch, x.device):
+    if not _c2c_supported(shape, rdt, batch, x.device):
         f = _fft_any(x, ndim, inverse)
         return f if float(scale) == 1.0 else cplx_rows(f, None, f.shape[-1], f.shape[-1], 0, scale)
     plan = get_plan(shape, rdt, batch, x.device)

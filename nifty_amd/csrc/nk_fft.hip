@@ -1610,6 +1610,19 @@ static int nk_run_c2c(const nk_plan* P, const void* in, void* out, int inverse, 
   return rc;
 }
 
+// the complex transform keeps a line of the FULL last axis in LDS, the real ones a line of half of it: a plan
+// nk_hartley takes may be one nk_fftn refuses (nk_plan_create leaves cc.lp.n == 0 then)
+extern "C" int nk_plan_c2c_ok(const nk_plan* P) { return P && P->cc.lp.n != 0 ? 1 : 0; }
+// dynamic LDS of the three c2c launches as nk_plan_create set them up (0: no such pass on this plan)
+extern "C" int nk_plan_c2c_lds(const nk_plan* P, int64_t lds[3]) {
+  if (!P || !lds) return nk_set_error(NK_ERR_INVALID, "nk_plan_c2c_lds: null argument");
+  const bool ok = P->cc.lp.n != 0;
+  lds[0] = ok ? (int64_t)P->lds_cc : 0;
+  lds[1] = ok && P->ndim == 3 ? (int64_t)P->lds_cm : 0;
+  lds[2] = ok && P->ndim >= 2 ? (int64_t)P->lds_cf : 0;
+  return NK_OK;
+}
+
 extern "C" int nk_fftn(const nk_plan* P, const void* in, void* out, int inverse, double scale, void* workspace,
                        void* stream) {
   (void)workspace;

@@ -85,7 +85,7 @@ def test_chirp_z_fallback_terminates_and_is_exact(monkeypatch):
 
     calls = []
 
-    def pow2_only(shape, dtype, batch=1, device=None):
+    def pow2_only(shape, dtype, batch=1, device=None, complex=False):
         n = int(shape[-1])
         return len(shape) == 1 and n & (n - 1) == 0 and n <= 4096
 

@@ -1,6 +1,10 @@
 """Host tests of tests/transform_cases.py -- the long-double reference, the derived bounds and the comparators that
 tests/test_fused_transforms_gpu.py asserts on the device -- and of the host emulation's outputs under the same
-comparators (tests/emu runs the kernels' phase functions thread by thread, on every route of the library)."""
+comparators (tests/emu runs the kernels' phase functions thread by thread, on every route of the library).  The second half
+does the same for the complex side (tests/test_complex_transforms_gpu.py): the complex reference against a direct mpmath DFT,
+the c2c and chirp-z bounds against scipy.fft and a numpy restatement of the chirp-z in the same precision on every shape and
+length -- and on the very inputs -- of the device tests, the accuracy of the host-built filter tables, and the lengths of
+the seam tests re-derived from the limits in the code."""
 import ctypes
 import os
 
@@ -325,3 +329,180 @@ def test_value_comparator_rejects_a_dropped_wavefront_partial(dtype):
     good = case.outputs["value"] + np.sum(e[::-1])
     assert tc.within_elem(good, value, bound)[0]
     assert not tc.within_elem(good - np.sum(e[0]), value, bound)[0]
+
+
+# ---- complex transforms: the reference, and the bounds against sound implementations in T -------------------------------
+@pytest.mark.parametrize("shape", [(2,), (30,), (64,), (4, 6), (6, 10), (2, 3, 4), (4, 2, 8)])
+def test_complex_long_double_reference_equals_a_direct_dft(shape):
+    x = tc.normal_complex(shape, np.float64, 0)
+    for inverse in (False, True):
+        ref = tc.fft_direct_mp(x, inverse)
+        got = tc.fft_ld(x, len(shape), inverse)
+        assert np.max(np.abs(got - ref)) < 1e-17 * np.max(np.abs(ref))
+        assert tc.err_l2c(np.conj(tc.fft_ld(np.conj(x), len(shape), not inverse)), ref) < 1e-17 * tc.l2c(ref)
+
+
+def test_c2c_set_up_restated():
+    """The figures the device tests assert: the strided passes that need more than 64 KiB, the longest lines."""
+    for dt, (shape, lds) in tc.C2C_BIG_LDS.items():
+        for batch in (1, 3):
+            assert tc.c2c_lds_bytes(shape, dt, batch)[2] == lds > 64 * 1024
+    (a, la), (b, lb) = tc.C2C_TWO_PLANS
+    assert tc.c2c_lds_bytes(a, np.float64)[2] == la > lb == tc.c2c_lds_bytes(b, np.float64)[2] > 64 * 1024
+    assert tc.c2c_lds_bytes((1000, 8), np.float64)[2] == 64000  # the listed shape stays just below
+    assert tc.c2c_longest(np.float64) == 8640 and tc.c2c_longest(np.float32) == 17280
+    for dt in DTYPES:
+        nl = tc.c2c_longest(dt)
+        assert nl + nl // 16 + 1 <= tc.c2c_line_limit(dt) and tc.c2c_lds_bytes((nl,), dt, 3)[0] > 64 * 1024
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_c2c_bound_holds_for_scipy_in_the_same_precision(dtype):
+    """every shape of the device test, its seeded batch of three, forward and inverse"""
+    u = tc.unit_roundoff(dtype)
+    for shape in tc.c2c_shapes(dtype):
+        x = tc.normal_complex((3,) + shape, dtype, 51)
+        rel = tc.c2c_rel_bound(shape, dtype)
+        for inverse in (False, True):
+            ref = tc.fft_ld(x, len(shape), inverse)
+            ok, e = tc.within_l2c(tc.fft_same_precision(x, len(shape), inverse), ref, rel * tc.l2c(ref))
+            print(f"ERR kind=c2c shape={'x'.join(map(str, shape))} dtype={np.dtype(dtype).name} mode=host/inv{int(inverse)} "
+                  f"err={e / tc.l2c(ref):.3e} bound={rel:.3e} err_u={e / tc.l2c(ref) / u:.2f}")
+            assert ok and e > 0.0, (shape, inverse, e, rel * tc.l2c(ref))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("shape", [(30,), (4096,), (15, 14), (9, 25, 28)])
+def test_c2c_impulse_reference_and_bound(shape, dtype):
+    bound = tc.c2c_impulse_elem_bound(shape, dtype)
+    for p in tc.impulse_positions(shape):
+        x = np.zeros(shape, dtype=tc.complex_dtype(dtype))
+        x[p] = 1.0
+        for inverse in (False, True):
+            ref = tc.impulse_reference_c2c(shape, p, inverse)
+            assert np.max(np.abs(tc.fft_ld(x, len(shape), inverse) - ref)) < 1e-17
+            ok, worst = tc.within_elem_c(tc.fft_same_precision(x, len(shape), inverse), ref, bound)
+            assert ok, (p, inverse, worst)
+            if np.max(np.abs(ref.imag)) > 0.5:  # the other direction must not pass
+                assert not tc.within_elem_c(tc.fft_same_precision(x, len(shape), not inverse), ref, bound)[0]
+
+
+def chirp_lengths(dtype):
+    """(n, m, kind) of every chirp-z length the device tests run in `dtype`"""
+    out = [(n, m, "bluestein") for n, m, only in tc.BLUESTEIN_LENGTHS if only is None or np.dtype(only) == np.dtype(dtype)]
+    out.append(tc.BLUESTEIN_GRID_STRIDE[:2] + ("bluestein",))
+    csize = 8 if np.dtype(dtype) == np.float32 else 16
+    seam = sorted({n for s in tc.SEAM_SHAPES for n in s if n % 2 or any(n % p == 0 for p in (11, 13, 17))})
+    for n in seam:
+        out += [(n, tc.smallest_m(n), "bluestein"), (n, tc.smallest_m(n), "composition")]
+    for n, kind in tc.SEAM_LENGTHS[np.dtype(dtype)]:
+        assert (tc.smallest_m(n) * csize <= 64 * 1024) == (kind == "one-launch")
+        out.append((n, tc.smallest_m(n), "bluestein" if kind == "one-launch" else "composition"))
+    return out
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_chirp_z_bounds_hold_for_the_restatement_in_the_same_precision(dtype):
+    """Every length of the device tests on their seeded rows: numpy's chirp-z with every intermediate in T stays inside
+    bluestein_rel_bound (tables of backend._bluestein_tables) and composition_rel_bound (filter spectrum transformed in T)."""
+    import torch
+
+    from nifty_amd import backend as B
+
+    u = tc.unit_roundoff(dtype)
+    cdt = torch.complex64 if np.dtype(dtype) == np.float32 else torch.complex128
+    for n, m, kind in chirp_lengths(dtype):
+        rows = 3 if n * m < 1 << 20 else 2
+        x = tc.normal_complex((rows, n), dtype, 52)
+        for inverse in (False, True):
+            wl, bl, bmax = tc.bluestein_filter_ld(n, m, inverse)
+            if kind == "bluestein":
+                w, bbr, _ = (t.numpy() for t in B._bluestein_tables(n, m, cdt, inverse, torch.device("cpu")))
+                bhat = bbr[tc.bit_reverse(m)]
+                w2, b2 = tc.bluestein_host_tables(n, m, dtype, inverse)
+                assert np.array_equal(w, w2) and np.array_equal(bhat, b2)
+            else:
+                w, _ = tc.bluestein_host_tables(n, m, dtype, inverse)
+                b = np.zeros(m, dtype=w.dtype)
+                b[:n] = w.conj()
+                b[m - n + 1:] = w.conj()[1:][::-1]
+                bhat = scipy_fft_in(b)
+            terr = tc.bluestein_table_error(bhat, n, m, inverse)
+            assert np.max(np.abs(w.astype(tc.CLD) - wl)) <= (tc.MU_W64 * tc.U64 + (u if np.dtype(dtype) == np.float32 else 0.0))
+            fn = tc.bluestein_rel_bound if kind == "bluestein" else tc.composition_rel_bound
+            for hartley in (0, 1, -1):
+                scale = 0.75 if hartley else 1.0
+                xin = np.ascontiguousarray(x.real) if hartley == -1 else x  # real rows with one of the Hartley ends
+                ref = tc.LD(scale) * tc.fft_ld(xin, 1, inverse)
+                if hartley:
+                    ref = ref.real + hartley * ref.imag
+                got = tc.bluestein_same_precision(xin, n, m, w, bhat, scale, hartley)
+                bound = fn(n, m, dtype, hartley=bool(hartley), inverse=inverse, table_err=terr)
+                e = float(np.max(tc.row_errors(got, ref, xin, n, scale)))
+                print(f"ERR kind={kind} n={n} m={m} dtype={np.dtype(dtype).name} mode=host/inv{int(inverse)}/h{hartley} err={e:.3e} "
+                      f"bound={bound:.3e} err_u={e / u:.2f} table_err_u={terr / u:.2f} bmax={bmax / np.sqrt(n):.3f}")
+                assert e <= bound and (e > 0.0 or n <= 2), (n, m, kind, inverse, hartley, e, bound)
+
+
+def scipy_fft_in(b):
+    import scipy.fft
+
+    out = scipy.fft.fft(b)
+    assert out.dtype == b.dtype
+    return out
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_host_filter_tables_are_as_accurate_as_the_bound_assumes(dtype):
+    """table_err of backend._bluestein_tables: rounded once in fp32 (the double transform behind it is far below u), and
+    inside the norm-wise bound of a double transform of L levels on the perturbed filter in fp64."""
+    u = tc.unit_roundoff(dtype)
+    for n, m, only in tc.BLUESTEIN_LENGTHS:
+        if only is not None and np.dtype(only) != np.dtype(dtype):
+            continue
+        for inverse in (False, True):
+            _, bhat = tc.bluestein_host_tables(n, m, dtype, inverse)
+            terr = tc.bluestein_table_error(bhat, n, m, inverse)
+            bmax = tc.bluestein_filter_ld(n, m, inverse)[2]
+            assert terr <= tc.host_table_error_ceiling(n, m, dtype, inverse), (n, m, terr / u)
+            assert 1.0 <= bmax / np.sqrt(n) <= 2.5 or n <= 2, (n, m, bmax)
+
+
+def test_chirp_z_comparator_rejects_wrong_rows():
+    """a swapped pair of outputs, the other direction, a dropped final chirp and a wrong filter entry all leave the bound"""
+    n, m, dtype = 211, 512, np.float32
+    x = tc.normal_complex((3, n), dtype, 52)
+    w, bhat = tc.bluestein_host_tables(n, m, dtype)
+    ref = tc.fft_ld(x, 1)
+    bound = tc.bluestein_rel_bound(n, m, dtype)
+    good = tc.bluestein_same_precision(x, n, m, w, bhat)
+    assert np.max(tc.row_errors(good, ref, x, n)) <= bound
+    sw = good.copy()
+    sw[1, 5], sw[1, 6] = good[1, 6], good[1, 5]
+    assert np.max(tc.row_errors(sw, ref, x, n)) > bound
+    assert np.max(tc.row_errors(np.conj(good), ref, x, n)) > bound
+    bad = bhat.copy()
+    bad[7] *= np.complex64(1.0 + 1e-3)  # one filter entry wrong in the fourth digit
+    assert np.max(tc.row_errors(tc.bluestein_same_precision(x, n, m, w, bad), ref, x, n)) > bound
+    nn = good.copy()
+    nn[2, 0] = np.nan
+    assert not np.max(tc.row_errors(nn, ref, x, n)) <= bound
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_seam_lengths_follow_from_the_limits_in_the_code(dtype):
+    """tc.SEAM_LENGTHS from the rules: the one-launch kernel takes rows of m complex values in 64 KiB, the composition a
+    padded length that nk_fftn takes (one line of m + m / 16 + 1 complex values in 144 KiB) up to the seam's own cap."""
+    from nifty_amd import backend as B
+
+    csize = 8 if np.dtype(dtype) == np.float32 else 16
+    m_one = B.BLUESTEIN_LDS_BYTES // csize
+    m_comp = max(m for m in (1 << k for k in range(2, 20)) if m + m // 16 + 1 <= tc.c2c_line_limit(dtype) and m <= B._CHIRP_MAX)
+    assert (m_one, m_comp) == ((4096, 8192) if csize == 16 else (8192, 16384))
+    (a, pa), (b, pb), (c, pc) = tc.SEAM_LENGTHS[np.dtype(dtype)]
+    # m = 2 n would serve the power of two n itself, which the planner takes: the longest REJECTED length is one below
+    assert (a, pa) == (m_one // 2 - 1, "one-launch") and tc.smallest_m(a) == m_one
+    assert (b, pb) == (m_one // 2 + 1, "composition") and tc.smallest_m(b) == 2 * m_one
+    assert (c, pc) == (m_comp // 2 - 1, "composition") and tc.smallest_m(c) == m_comp and tc.smallest_m(m_comp // 2 + 1) == 2 * m_comp
+    for n in (a, b, c, m_comp // 2 + 1):  # none of them is a length of the native planner
+        assert n % 2 == 1

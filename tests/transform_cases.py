@@ -65,6 +65,55 @@ IMPULSES.  A unit impulse at p gives scale * cas(2 pi sum_d k_d p_d / n_d).  Eve
 value of modulus 1 by a twiddle (additions of zero are exact; a radix-R odd stage multiplies by one constant and one
 twiddle: 2 (mu + sqrt2 gamma_2) <= 2 eta_table), the untangle adds two values of modulus <= 1 (its level counted twice), so a
 complex coefficient errs by (levels + 2) eta_table and Re +- Im by sqrt2 times that, per ELEMENT.
+
+COMPLEX TRANSFORMS (nk_fftn; tests/test_complex_transforms_gpu.py).  Reference: scipy.fft on complex256 (fft_ld), checked
+against a direct mpmath DFT (fft_direct_mp).  k_c2c_contig / k_c2c_strided run the generic stages of nk_core.h
+(nk_dif_stage) on every axis at FULL length: no real-pair untangle, no two-level pass.
+  => c2c_rel_bound(shape) = SLACK * sum of eta(p) over the prime factors p of every axis + u,
+the u for the one product with (T)scale (the tests use scales that T represents exactly).
+  Written down, not hidden: a radix-4 / radix-8 stage of nk_dif_stage reads ONE table entry w and forms w^2 .. w^(R-1) by
+  repeated products, |w^r^ - w^r| <= r u + (r - 1) sqrt2 gamma_2.  Over the R outputs of a butterfly that is 5.0 u (R = 4)
+  and 13.7 u (R = 8) in the root mean square against the mu = u of a table entry, so the worst case of a radix-8 stage on
+  paper is about 20 u where its three levels are counted with 15 u (radix 4: 9.8 u against 10 u).  The bound is kept as
+  the table-twiddle rule gives it -- the tighter figure -- and is not widened for this.
+* c2c_impulse_elem_bound: a unit impulse passes ONE non-zero value of modulus 1 through every stage (additions of zero
+  are exact): one twiddle product per level (an odd stage: a constant and a twiddle, 2 eta_table), no untangle, and the
+  complex coefficient itself is compared (no Re +- Im, no sqrt2): (levels + 2 #odd) eta_table + u per ELEMENT.
+
+CHIRP-Z (nk_bluestein_rows, one launch; backend._fft_last_axis_any, three native transforms).  n points, padded to m = 2^L.
+With w_j = exp(-+ i pi j^2 / n) and the cyclic filter b_j = conj(w)_|j|:  X_k = w_k (a * b)_k,  a = x . w zero-padded.
+Tables (backend._bluestein_tables / _chirp): angles from j^2 mod 2n in integers, evaluated in DOUBLE on the host:
+    theta^ = fl(fl(j^2 mod 2n) fl(pi / n)): relative 2.4 u64 (pi, the quotient, the product) of theta <= 2 pi -> 15 u64,
+    cos / sin <= 1 ulp each -> sqrt2 u64;            mu_w  = 17 u64 (+ u when rounded to fp32)
+    exp(-2 pi i k / m), k / m exact, theta <= pi:    mu_tw = 5 u64  (+ u when rounded to fp32)
+  so in fp64 the level of the one-launch kernel costs eta_b = mu_tw + gamma_4 = 9 u, not the 5 u of a long-double table
+  (fp32: 5 u as before).  Its radix-4 butterflies read BOTH levels' twiddles from the table (tw[j s1], tw[j s2]); the +-i
+  rotations and the conjugation of the inverse levels are exact.
+  The filter spectrum bhat the kernel multiplies with is itself a product of a transform (numpy's, in double, for the
+  one-launch kernel; nk_fftn in T for the composition).  Its error is a property of the TABLE handed to the kernel, not
+  of the kernel: table_err = max_k |bhat^_k - bhat_k| / Bmax, Bmax = max_k |bhat_k|, both from the filter spectrum built
+  here in long double (bluestein_filter_ld, bluestein_table_error); a table rounded once has table_err <= u.  The tests
+  measure it on the table they pass and hand it to the bound; tests/test_transform_cases.py pins it for the host tables.
+Chain, first order, absolute, P = sqrt2 gamma_2 one complex product:
+    a^ = fl(x w^)                       ||da||  <= (mu_w + P) ||x||                           (||a|| = ||x||)
+    A^ = DIF levels                     ||dA||  <= (L eta_b + mu_w + P) sqrt m ||x||
+    p^ = fl(A^ bhat^)                   ||dp||  <= Bmax (L eta_b + mu_w + 2 P + table_err) sqrt m ||x||
+    c^ = DIT levels (unnormalised)      ||dc||  <= m Bmax (2 L eta_b + mu_w + 2 P + table_err) ||x||
+    crop to n (no larger), times w^, times (T)(scale / m) (m a power of two: exact when scale is; one product, and one
+    more u for a scale T does not represent)
+    ||X^ - X||_2 <= |scale| Bmax E_conv ||x||_2,   E_conv = 2 L eta_b + 2 mu_w + table_err + 3 P + 2 u
+  ||p|| <= Bmax ||A|| and Parseval carry the norms; a real input row only saves roundings in the first product.
+  Relative to ||X||_2 = |scale| sqrt n ||x||_2 of the COMPLEX transform (the tests bound the absolute error by that norm
+  row by row, because Re X +- Im X of a complex row can be much smaller than X):
+    bluestein_rel_bound = SLACK E_conv Bmax / sqrt n          (Bmax = 2.0 .. 2.3 sqrt n; 310 u at m = 8192 in fp32)
+  Hartley end Re X + s Im X: |d Re| + |d Im| <= sqrt2 |dX|, one addition and the product with scale: sqrt2 (E + 2 u).
+  composition_rel_bound: the same chain with each run of L levels replaced by nk_fftn on (m,), c2c_rel_bound((m,)) (its
+  + u is the product with scale = 1 / m), and the three nk_cplx_rows products (scale = 1: exact):
+    E_conv = 2 c2c_rel_bound((m,)) + 2 mu_w + table_err + 3 P.
+  Axes compose: every axis transform has norm sqrt n_axis, so relative errors ADD over the axes of the seam's N-D walk
+  (seam_rel_bound; one more SLACK for the cross terms, one u for a separate scale launch).
+* nk_cplx_rows per ELEMENT: scale (re wr - im wi) is two products, one subtraction, one product: gamma_3 times the sum
+  of the absolute terms (a contraction into fma only removes roundings); mode 2, scale (re + sgn im): gamma_2.
 """
 import functools
 import math
@@ -177,8 +226,8 @@ def hartley_direct_mp(x, sign=1):
     return out
 
 
-def impulse_reference(shape, p, sign=1):
-    """cas(2 pi sum k_d p_d / n_d) for every k, the argument reduced in integers (modulo the common denominator)."""
+def impulse_theta(shape, p):
+    """2 pi sum k_d p_d / n_d for every k in long double, the argument reduced in integers (modulo the common denominator)."""
     M = 1
     for n in shape:
         M = M * n // math.gcd(M, n)
@@ -187,7 +236,12 @@ def impulse_reference(shape, p, sign=1):
         k = np.arange(n, dtype=np.int64).reshape([-1 if e == d else 1 for e in range(len(shape))])
         m = (m + k * (int(p[d]) * (M // n) % M)) % M
     two_pi = LD(2) * np.arctan(LD(1)) * 4
-    th = two_pi * m.astype(LD) / LD(M)
+    return two_pi * m.astype(LD) / LD(M)
+
+
+def impulse_reference(shape, p, sign=1):
+    """cas(2 pi sum k_d p_d / n_d) for every k."""
+    th = impulse_theta(shape, p)
     return np.cos(th) - sign * np.sin(th)  # Re F + sign Im F of exp(-i theta)
 
 
@@ -657,3 +711,325 @@ def compare(case, ref, got):
             raise KeyError(kind)
         rows.append((name, float(e), float(bound), bool(ok)))
     return rows
+
+
+# ---- complex transforms: nk_fftn, nk_bluestein_rows, the chirp-z composition (module docstring) ----------------------
+CLD = np.clongdouble
+
+
+def complex_dtype(dtype):
+    return np.complex64 if np.dtype(dtype) in (np.dtype(np.float32), np.dtype(np.complex64)) else np.complex128
+
+
+def normal_complex(shape, dtype, seed):
+    """seeded complex normal data in T: the inputs the device tests and the host tests of the bounds share"""
+    rng = np.random.default_rng(seed)
+    return (rng.normal(size=shape) + 1j * rng.normal(size=shape)).astype(complex_dtype(dtype))
+
+
+def fft_ld(x, ndim, inverse=False):
+    """Unnormalised c2c transform over the last `ndim` axes in long double (exp(+i ..) for inverse)."""
+    x = np.asarray(x).astype(CLD)
+    axes = tuple(range(x.ndim - ndim, x.ndim))
+    F = scipy.fft.ifftn(x, axes=axes, norm="forward") if inverse else scipy.fft.fftn(x, axes=axes)
+    assert F.dtype == np.complex256
+    return F
+
+
+def fft_same_precision(x, ndim, inverse=False):
+    """scipy.fft run in the dtype of x: what a sound transform in T does"""
+    axes = tuple(range(x.ndim - ndim, x.ndim))
+    F = scipy.fft.ifftn(x, axes=axes, norm="forward") if inverse else scipy.fft.fftn(x, axes=axes)
+    assert F.dtype == x.dtype
+    return F
+
+
+def fft_direct_mp(x, inverse=False):
+    """Direct DFT sum with mpmath (50 digits) -- grids of <= 64 points."""
+    import mpmath
+
+    mpmath.mp.dps = 50
+    x = np.asarray(x)
+    assert x.size <= 64
+    out = np.empty(x.shape, dtype=CLD)
+    for k in np.ndindex(*x.shape):
+        acc = mpmath.mpc(0)
+        for p in np.ndindex(*x.shape):
+            th = 2 * mpmath.pi * sum(mpmath.mpf(int(a) * int(b)) / n for a, b, n in zip(k, p, x.shape))
+            acc += mpmath.mpc(float(x[p].real), float(x[p].imag)) * mpmath.expj(th if inverse else -th)
+        out[k] = LD(mpmath.nstr(acc.real, 30)) + 1j * LD(mpmath.nstr(acc.imag, 30))
+    return out
+
+
+def impulse_reference_c2c(shape, p, inverse=False):
+    """exp(-+ 2 pi i sum k_d p_d / n_d): the transform of a unit impulse at p"""
+    th = impulse_theta(shape, p)
+    return np.cos(th) + (1j if inverse else -1j) * np.sin(th)
+
+
+def l2c(x):
+    """2-norm of a real or complex array in long double"""
+    return float(np.sqrt(np.sum(np.abs(np.asarray(x).astype(CLD)) ** 2)))
+
+
+def err_l2c(got, ref):
+    return l2c(np.asarray(got).astype(CLD) - ref)
+
+
+def within_l2c(got, ref, bound):
+    e = err_l2c(got, ref)
+    return bool(np.isfinite(e) and e <= bound), e
+
+
+def within_elem_c(got, ref, bound):
+    """(ok, worst error / bound): element-wise comparator of complex (or real) arrays; a NaN anywhere fails"""
+    d = np.abs(np.asarray(got).astype(CLD) - ref)
+    worst = float(np.max(d / bound)) if d.size else 0.0
+    return bool(np.isfinite(worst) and worst <= 1.0), worst
+
+
+def c2c_levels(shape):
+    fs = [p for n in shape for p in factor(n)]
+    return fs.count(2), [p for p in fs if p != 2]
+
+
+def c2c_rel_bound(shape, dtype):
+    """E with ||F^(x) - F(x)||_2 <= E ||F(x)||_2 for nk_fftn in `dtype` (scale exactly representable in T)."""
+    u = unit_roundoff(dtype)
+    twos, odd = c2c_levels(shape)
+    return SLACK * (twos * eta(2, u) + sum(eta(p, u) for p in odd)) + u
+
+
+def c2c_impulse_elem_bound(shape, dtype):
+    u = unit_roundoff(dtype)
+    twos, odd = c2c_levels(shape)
+    return SLACK * (twos + 2 * len(odd)) * eta(2, u) + u
+
+
+# the c2c set-up of nk_plan_create restated (nk_fft.hip; nk_pick_strided_tile of nk_plan.h without its environment knobs)
+def pick_strided_tile(n, inner, csize, outer):
+    def grow(t, budget):
+        while 2 * t <= inner and n * 2 * t * csize <= budget and 2 * t * csize <= 256:
+            t *= 2
+        return t
+
+    t = grow(1, 128 * 1024)
+    if t * csize < 64:
+        t = grow(t, 152 * 1024)
+    while t > 4 and outer * -(-inner // t) < 256:
+        t //= 2
+    return t
+
+
+def c2c_lds_bytes(shape, dtype, batch=1):
+    """dynamic LDS of (k_c2c_contig, k_c2c_strided middle axis, k_c2c_strided first axis); 0 = no such pass"""
+    csize = 8 if np.dtype(dtype) == np.float32 else 16
+    nl = shape[-1]
+    na = shape[0] if len(shape) >= 2 else 1
+    nm = shape[1] if len(shape) == 3 else 1
+    line = (nl + nl // 16 + 1) * csize
+    tile = max(1, min(32 * 1024 // line, -(-2048 // nl)))
+    tile = min(tile, batch * na * nm)
+    mid = nm * pick_strided_tile(nm, nl, csize, batch * na) * csize if len(shape) == 3 else 0
+    first = na * pick_strided_tile(na, nm * nl, csize, batch) * csize if len(shape) >= 2 else 0
+    return tile * line, mid, first
+
+
+def c2c_line_limit(dtype):
+    """complex values of one padded line the contiguous c2c pass keeps in LDS: 144 KiB"""
+    return 144 * 1024 // (8 if np.dtype(dtype) == np.float32 else 16)
+
+
+def is_smooth(n):
+    for p in (2, 3, 5, 7):
+        while n % p == 0:
+            n //= p
+    return n == 1
+
+
+def c2c_longest(dtype):
+    """the largest even 7-smooth nl with nl + nl / 16 + 1 <= 9216 (fp64) / 18432 (fp32)"""
+    lim = c2c_line_limit(dtype)
+    for nl in range(lim, 1, -1):
+        if nl % 2 == 0 and nl + nl // 16 + 1 <= lim:
+            r = nl
+            for p in (2, 3, 5, 7):
+                while r % p == 0:
+                    r //= p
+            if r == 1:
+                return nl
+    raise AssertionError
+
+
+C2C_SHAPES = [(2,), (6,), (30,), (500,), (1024,), (4096,), (6, 10), (15, 14), (64, 64), (7, 500), (1000, 8), (6, 5, 14), (9, 25, 28),
+              (64, 6, 128)]
+# one shape per dtype whose strided (first-axis) pass needs more than 64 KiB of LDS: tile 4 (rows of 64 B / 32 B), n * 4 * csize
+C2C_BIG_LDS = {np.dtype(np.float64): ((1280, 8), 81920), np.dtype(np.float32): ((2560, 8), 81920)}
+# two fp64 plans that both need more than 64 KiB in k_c2c_strided<double>, the first more than the second
+C2C_TWO_PLANS = (((2048, 8), 131072), ((1280, 8), 81920))
+
+
+def c2c_shapes(dtype):
+    return C2C_SHAPES + [C2C_BIG_LDS[np.dtype(dtype)][0], (c2c_longest(dtype),)]
+
+
+# ---- chirp-z ------------------------------------------------------------------------------------------------------------
+MU_W64, MU_TW64 = 17.0, 5.0  # host evaluation of the chirp / of the level twiddles in double, in units of u64
+
+
+def smallest_m(n):
+    return 1 << max(2, (2 * n - 2).bit_length())
+
+
+def bit_reverse(m):
+    bits = m.bit_length() - 1
+    rev = np.zeros(m, dtype=np.int64)
+    for bit in range(bits):
+        rev |= ((np.arange(m) >> bit) & 1) << (bits - 1 - bit)
+    return rev
+
+
+@functools.lru_cache(maxsize=64)
+def bluestein_filter_ld(n, m, inverse=False):
+    """(chirp w[n], spectrum bhat[m] of the cyclic filter in natural order, Bmax = max |bhat|) in long double"""
+    k = np.arange(n, dtype=np.int64)
+    ang = (LD(4) * np.arctan(LD(1))) * (k * k % (2 * n)).astype(LD) / LD(n)
+    w = np.cos(ang) + (1j if inverse else -1j) * np.sin(ang)
+    b = np.zeros(m, dtype=CLD)
+    b[:n] = w.conj()
+    b[m - n + 1:] = w.conj()[1:][::-1]
+    bhat = scipy.fft.fft(b)
+    assert bhat.dtype == np.complex256
+    for a in (w, bhat):
+        a.setflags(write=False)
+    return w, bhat, float(np.max(np.abs(bhat)))
+
+
+def bluestein_table_error(bhat_used, n, m, inverse=False):
+    """max_k |bhat_used_k - bhat_k| / Bmax of a filter spectrum in NATURAL order as a kernel is handed it"""
+    _, bhat, bmax = bluestein_filter_ld(n, m, inverse)
+    return float(np.max(np.abs(np.asarray(bhat_used).astype(CLD) - bhat))) / bmax
+
+
+def host_table_error_ceiling(n, m, dtype, inverse=False):
+    """ceiling of bluestein_table_error for the tables backend._bluestein_tables builds on the host: rounded once in fp32
+    (the double transform behind it is far below u); in fp64 the norm-wise bound of a double transform of L levels on the
+    filter built from the perturbed chirp (every entry within mu_w), taken per element"""
+    if np.dtype(dtype) == np.float32:
+        return 1.001 * 2.0 ** -24
+    L = m.bit_length() - 1
+    bmax = bluestein_filter_ld(n, m, inverse)[2]
+    return (SLACK * L * eta(2, U64) * math.sqrt(m * (2.0 * n - 1)) + MU_W64 * U64 * (2 * n - 1)) / bmax
+
+
+def device_filter_l2_bound(n, m, dtype, inverse=False):
+    """||fb^ - bhat||_2 of the filter spectrum the composition transforms ON THE DEVICE with nk_fftn: the filter's entries are
+    the conjugate chirp rounded to T (each within mu_w, ||db|| <= mu_w ||b||, carried by the transform as mu_w ||bhat||) and
+    the transform itself errs by c2c_rel_bound((m,))"""
+    bhat = bluestein_filter_ld(n, m, inverse)[1]
+    return (c2c_rel_bound((m,), dtype) + _table_mu(dtype, MU_W64)) * l2c(bhat)
+
+
+def _table_mu(dtype, host_u64):
+    return (2.0 ** -24 if np.dtype(dtype) == np.float32 else 0.0) + host_u64 * U64
+
+
+def _chirp_tail(e_conv, n, m, dtype, hartley, inverse):
+    u = unit_roundoff(dtype)
+    e = SLACK * e_conv * bluestein_filter_ld(n, m, inverse)[2] / math.sqrt(n)
+    return math.sqrt(2.0) * (e + 2 * u) if hartley else e
+
+
+def bluestein_rel_bound(n, m, dtype, real_in=False, hartley=False, inverse=False, table_err=None):
+    """E with ||X^ - X||_2 <= E |scale| sqrt n ||x||_2 for one row of nk_bluestein_rows (module docstring, CHIRP-Z).
+    real_in saves roundings only; table_err: bluestein_table_error of the table in use (None: rounded once, u)."""
+    u = unit_roundoff(dtype)
+    L = m.bit_length() - 1
+    assert m == 1 << L and m >= max(4, 2 * n - 1)
+    level = _table_mu(dtype, MU_TW64) + gamma(4, u)
+    prod = math.sqrt(2.0) * gamma(2, u)
+    tab = u if table_err is None else table_err
+    e_conv = 2 * L * level + 2 * _table_mu(dtype, MU_W64) + tab + 3 * prod + 2 * u
+    return _chirp_tail(e_conv, n, m, dtype, hartley, inverse)
+
+
+def composition_rel_bound(n, m, dtype, hartley=False, inverse=False, table_err=None):
+    """the same for the three-transform composition of backend._fft_last_axis_any (nk_fftn on (m,) twice, nk_cplx_rows)"""
+    u = unit_roundoff(dtype)
+    prod = math.sqrt(2.0) * gamma(2, u)
+    tab = u if table_err is None else table_err
+    e_conv = 2 * c2c_rel_bound((m,), dtype) + 2 * _table_mu(dtype, MU_W64) + tab + 3 * prod
+    return _chirp_tail(e_conv, n, m, dtype, hartley, inverse)
+
+
+def seam_rel_bound(axis_bounds, dtype, separate_scale=False):
+    """relative errors of the axis transforms add (every one has norm sqrt n_axis; a Hartley end is part of the last axis'
+    own bound), one more SLACK for their cross terms; separate_scale: one more launch that multiplies by scale"""
+    return SLACK * sum(axis_bounds) + (unit_roundoff(dtype) if separate_scale else 0.0)
+
+
+def bluestein_host_tables(n, m, dtype, inverse=False):
+    """(w[n], bhat[m] in natural order) in T as backend._bluestein_tables builds them: angles and the filter's transform
+    in double on the host, rounded to T"""
+    k = np.arange(n, dtype=np.int64)
+    ang = (k * k % (2 * n)).astype(np.float64) * (np.pi / n)
+    w = np.exp(1j * ang if inverse else -1j * ang)
+    b = np.zeros(m, dtype=np.complex128)
+    b[:n] = w.conj()
+    b[m - n + 1:] = w.conj()[1:][::-1]
+    cdt = complex_dtype(dtype)
+    return w.astype(cdt), np.fft.fft(b).astype(cdt)
+
+
+def bluestein_same_precision(x, n, m, w, bhat, scale=1.0, hartley=0):
+    """The chirp-z restated with numpy in T = the dtype of the tables, every intermediate cast to T: what a sound
+    implementation does.  x: rows x n (real or complex); w[n], bhat[m] (natural order) in T."""
+    cdt = w.dtype
+    rdt = np.float32 if cdt == np.complex64 else np.float64
+    x = np.asarray(x)
+    a = np.zeros(x.shape[:-1] + (m,), dtype=cdt)
+    a[..., :n] = (x.astype(cdt) * w).astype(cdt)
+    A = scipy.fft.fft(a).astype(cdt)
+    P = (A * bhat).astype(cdt)
+    c = scipy.fft.ifft(P).astype(cdt)
+    v = (c[..., :n] * w).astype(cdt)
+    if hartley:
+        return (rdt(scale) * (v.real + rdt(hartley) * v.imag)).astype(rdt)
+    return (v * rdt(scale)).astype(cdt)
+
+
+def row_errors(got, ref, x, n, scale=1.0):
+    """per row: ||got - ref||_2 / (|scale| sqrt n ||x||_2) -- the quantity the chirp-z bounds limit (0 for a zero row that
+    comes out as zeros, inf for one that does not)"""
+    d = np.abs(np.asarray(got).astype(CLD) - ref) ** 2
+    e = np.sqrt(np.sum(d.reshape(-1, n), axis=1).astype(LD))
+    nx = np.sqrt(np.sum((np.abs(np.asarray(x).astype(CLD)) ** 2).reshape(-1, n), axis=1).astype(LD)) * LD(abs(scale) * math.sqrt(n))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(nx > 0, e / nx, np.where(e > 0, np.inf, 0.0))
+    return np.asarray(r, dtype=np.float64)
+
+
+def structured_rows(n, dtype, real=False):
+    """impulses at 0, n / 2 and n - 1, the constant and one exponential exp(2 pi i q j / n) (real: its cosine), rounded to T"""
+    pos = sorted({0, n // 2, n - 1})
+    x = np.zeros((len(pos) + 2, n), dtype=np.complex128)
+    for r, p in enumerate(pos):
+        x[r, p] = 1.0
+    x[len(pos)] = 1.0 if real else 1.0 - 0.5j
+    q = min(3, n - 1)
+    x[len(pos) + 1] = np.exp(2j * np.pi * ((q * np.arange(n)) % n) / n)
+    return np.ascontiguousarray(x.real.astype(dtype) if real else x.astype(complex_dtype(dtype)))
+
+
+# (n, m, only dtype or None): nk_bluestein_rows lengths -- the smallest m, both parities of log2 m, m = 2 n, the LDS limits
+# of both dtypes, twice and four times the smallest m
+BLUESTEIN_LENGTHS = [(1, 4, None), (2, 4, None), (3, 8, None), (5, 16, None), (11, 32, None), (17, 64, None), (32, 64, None),
+                     (33, 128, None), (211, 512, None), (1009, 2048, None), (2048, 4096, None), (4096, 8192, np.float32),
+                     (11, 64, None), (11, 128, None)]
+BLUESTEIN_ROW_SWEEPS = [(11, 32), (211, 512)]
+BLUESTEIN_GRID_STRIDE = (1500, 4096, 2051)  # more than 2048 row groups of R = 1 row
+# rejected lengths the array seam is tested at, with the path each takes (per dtype): the hand-over at the 64 KiB row, the
+# longest the composition serves (4095: m = 8192, the longest c2c line in fp64; 8191: m = 16384 = the seam's own cap)
+SEAM_LENGTHS = {np.dtype(np.float64): [(2047, "one-launch"), (2049, "composition"), (4095, "composition")],
+                np.dtype(np.float32): [(4095, "one-launch"), (4097, "composition"), (8191, "composition")]}
+SEAM_SHAPES = [(63,), (63, 54), (10, 11), (13, 17, 6)]
