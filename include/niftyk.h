@@ -652,6 +652,51 @@ int nk_nufft_interp(const nk_nufft_plan* p, const void* grid, void* pts, int dty
 int nk_nufft_crop(const nk_nufft_plan* p, const void* grid, void* out, int dtype, void* stream);
 int nk_nufft_pad(const nk_nufft_plan* p, const void* in, int in_complex, void* grid, int dtype, void* stream);
 
+/* ---- sampling: LinearInterpolator (reference operators/linear_interpolation.py, which writes the scipy coo matrix down) on a
+ *      periodic grid of 1-3 axes of lengths n, matrix-free (nifty_amd.sampling_operators.InterpolationPlan builds every array on
+ *      the host, once per operator; 8 ndim + 24 bytes per point at most, nothing per grid cell):
+ *   points   SORTED stably by base cell: cell[npoints] = flat C-order index of the base cell (floor(pos) mod n per axis),
+ *            frac[npoints][ndim] = pos - floor(pos) (fp64, in [0, 1)), perm[npoints] = original index of every sorted point
+ *   cells    cell_start[ncells + 1] = first sorted point of every OCCUPIED cell (ascending cell index; the cell itself is
+ *            cell[cell_start[c]]); long_cell[nlong] = the occupied cells holding more than 128 points
+ *   corner m of a point (m = 0 .. 2^ndim - 1, axis 0 the slowest bit) is the grid point (base_a + m_a) mod n_a, its weight
+ *   prod_a (m_a ? frac_a : 1 - frac_a), the product taken in axis order.
+ * nk_sample_times  : pts[perm[k]] = sum_m w_km grid[corner_km], the 2^ndim products added in corner order by one thread
+ * nk_sample_adjoint: grid = the transpose applied to pts (original order).  2^ndim stream-ordered passes, one per corner, in
+ *                    corner order; in a pass every occupied cell adds sum_k w_km pts[perm[k]] over its points into
+ *                    grid[cell + m] by a plain read-modify-write (distinct cells write distinct outputs).  The sum is formed
+ *                    in list order by one thread, or for a long cell by one workgroup: thread t takes the list positions t,
+ *                    t + 256, ..., the partial sums are joined by a xor butterfly over each wavefront and the wavefronts in
+ *                    order.  Every cell of the grid is written (zeros included).  NK_F32 needs the scratch `acc` (one double
+ *                    per grid cell, caller-owned): the sums stay fp64 until one final rounding; NK_F64 ignores it.
+ * Data in `dtype` (NK_F32 / NK_F64), every product and sum fp64 without contraction, no atomics: bit-reproducible.  The plan's
+ * device arrays are trusted (host-built) but cannot address outside the grid or the points; sizes are validated before any
+ * launch. */
+typedef struct nk_sample_plan {
+  int32_t ndim;
+  int64_t n[3];
+  int64_t npoints, ncells, nlong;
+  const int64_t* cell;
+  const double* frac;
+  const int64_t* perm;
+  const int64_t* cell_start;
+  const int64_t* long_cell;
+} nk_sample_plan;
+int nk_sample_times(const nk_sample_plan* p, const void* grid, void* pts, int dtype, void* stream);
+int nk_sample_adjoint(const nk_sample_plan* p, const void* pts, void* grid, double* acc, int dtype, void* stream);
+/* RegriddingOperator (reference operators/regridding_operator.py:79-103) along ONE axis of an (outer, n, inner) view, no wrap:
+ * nk_regrid_times  : out[o][j][i] = in[o][b_j][i] (1 - frac_j) + in[o][b_j + 1][i] frac_j    (in: n_old >= 2, out: n_new <= n_old;
+ *                    bindex[n_new] in [0, n_old - 2], frac[n_new] may exceed 1 at the clamped end)
+ * nk_regrid_adjoint: the exact transpose, output-driven (in: n_new, out: n_old): rstart[n_old + 1], rstart[i] = first j with
+ *                    b_j >= i (b is non-decreasing); old cell i adds in[j] (1 - frac_j) over rstart[i] <= j < rstart[i + 1],
+ *                    then in[j] frac_j over rstart[i - 1] <= j < rstart[i], ascending j.
+ * fp64 arithmetic without contraction; `in_dtype` / `out_dtype` may differ, so that the axes of a multi-axis regridding pass
+ * fp64 intermediates and the result is rounded once. */
+int nk_regrid_times(int64_t outer, int64_t n_old, int64_t n_new, int64_t inner, const int64_t* bindex, const double* frac,
+                    const void* in, int in_dtype, void* out, int out_dtype, void* stream);
+int nk_regrid_adjoint(int64_t outer, int64_t n_old, int64_t n_new, int64_t inner, const int64_t* rstart, const double* frac,
+                      const void* in, int in_dtype, void* out, int out_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,7 @@ from .operators import (Adder, BlockDiagonalOperator, ChainOperator, Contraction
                         Variable, VdotOperator, WienerFilterCurvature, ducktape, makeOp)
 from .los_response import LOSResponse  # noqa: F401
 from .nufft import Gridder, Nufft  # noqa: F401
+from .sampling_operators import LinearInterpolator, RegriddingOperator  # noqa: F401
 from .optimize_kl import optimize_kl  # noqa: F401
 from .parallel import shareRange  # noqa: F401
 from . import utilities  # noqa: E402,F401

@@ -59,6 +59,13 @@ class NufftPlan(ctypes.Structure):
                 ("n_items", _i64), ("item", _vp), ("n_split", _i64), ("split_tile", _vp), ("split_slab", _vp), ("corr", _vp)]
 
 
+class SamplePlan(ctypes.Structure):
+    """Mirror of ``struct nk_sample_plan`` (include/niftyk.h)."""
+
+    _fields_ = [("ndim", ctypes.c_int32), ("n", _i64 * 3), ("npoints", _i64), ("ncells", _i64), ("nlong", _i64), ("cell", _vp),
+                ("frac", _vp), ("perm", _vp), ("cell_start", _vp), ("long_cell", _vp)]
+
+
 # name -> (restype, argtypes); the list is checked against include/niftyk.h by tests/test_abi.py
 SIGNATURES = {
     "nk_last_error": (ctypes.c_char_p, []),
@@ -134,6 +141,10 @@ SIGNATURES = {
     "nk_nufft_interp": (_i, [ctypes.POINTER(NufftPlan), _vp, _vp, _i, _vp]),
     "nk_nufft_crop": (_i, [ctypes.POINTER(NufftPlan), _vp, _vp, _i, _vp]),
     "nk_nufft_pad": (_i, [ctypes.POINTER(NufftPlan), _vp, _i, _vp, _i, _vp]),
+    "nk_sample_times": (_i, [ctypes.POINTER(SamplePlan), _vp, _vp, _i, _vp]),
+    "nk_sample_adjoint": (_i, [ctypes.POINTER(SamplePlan), _vp, _vp, _vp, _i, _vp]),
+    "nk_regrid_times": (_i, [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _i, _vp, _i, _vp]),
+    "nk_regrid_adjoint": (_i, [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     # batched launches: per-member arguments are host arrays of `count` device pointers (ptr_array)
     "nk_plan_batch_ok": (_i, [_vp]),
     "nk_hartley_fused_batch": (_i, [_vp, ctypes.POINTER(Fuse), _i, _i, _vp, _vp]),

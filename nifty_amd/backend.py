@@ -614,6 +614,54 @@ class NufftDevicePlan:
         return grid
 
 
+class SampleDevicePlan:
+    """Device copy of a ``sampling_operators.InterpolationPlan`` (the arrays of ``nk_sample_plan``).  The two launches of
+    LinearInterpolator on real tensors: gather (TIMES) and the per-corner passes of its transpose (ADJOINT_TIMES)."""
+
+    _keys = ("cell", "frac", "perm", "cell_start", "long_cell")
+
+    def __init__(self, plan, device):
+        self._arrays = {k: torch.from_numpy(np.ascontiguousarray(getattr(plan, k))).to(device) for k in self._keys}
+        self.shape, self.npoints = tuple(plan.shape), int(plan.npoints)
+        n3 = (ctypes.c_int64 * 3)(*(list(plan.shape) + [1] * (3 - len(plan.shape))))
+        self.c = L.SamplePlan(ndim=len(plan.shape), n=n3, npoints=plan.npoints, ncells=len(plan.cell_start) - 1,
+                              nlong=len(plan.long_cell), **{k: ptr(self._arrays[k]) for k in self._keys})
+
+    def times(self, x):
+        """points [npoints] (the caller's order) = the grid x (real, contiguous) interpolated (nk_sample_times)"""
+        _require_device(x)
+        y = torch.empty(self.npoints, dtype=x.dtype, device=x.device)
+        L.check(L.load().nk_sample_times(ctypes.byref(self.c), x.data_ptr(), y.data_ptr(), dtype_code(x), _stream()),
+                "nk_sample_times")
+        return y
+
+    def adjoint(self, y):
+        """grid = the transpose applied to the points y (real, contiguous) (nk_sample_adjoint); fp32: fp64 sums in a
+        transient scratch of the grid's size, rounded once"""
+        _require_device(y)
+        out = torch.empty(self.shape, dtype=y.dtype, device=y.device)
+        acc = torch.empty(out.numel(), dtype=torch.float64, device=y.device) if y.dtype == torch.float32 else None
+        L.check(L.load().nk_sample_adjoint(ctypes.byref(self.c), y.data_ptr(), out.data_ptr(), ptr(acc), dtype_code(y),
+                                           _stream()), "nk_sample_adjoint")
+        return out
+
+
+def regrid_axis(x, outer, n_in, n_out, inner, table, frac, out_dtype, adjoint):
+    """One axis of RegriddingOperator on the (outer, n_in, inner) view of the contiguous real tensor x -> flat tensor of
+    outer * n_out * inner entries of `out_dtype` (nk_regrid_times with table = bindex; nk_regrid_adjoint with rstart)."""
+    _require_device(x, table, frac)
+    out = torch.empty(outer * n_out * inner, dtype=out_dtype, device=x.device)
+    lib = L.load()
+    if adjoint:
+        rc = lib.nk_regrid_adjoint(outer, n_out, n_in, inner, table.data_ptr(), frac.data_ptr(), x.data_ptr(), dtype_code(x),
+                                   out.data_ptr(), _DT[out_dtype], _stream())
+    else:
+        rc = lib.nk_regrid_times(outer, n_in, n_out, inner, table.data_ptr(), frac.data_ptr(), x.data_ptr(), dtype_code(x),
+                                 out.data_ptr(), _DT[out_dtype], _stream())
+    L.check(rc, "nk_regrid_adjoint" if adjoint else "nk_regrid_times")
+    return out
+
+
 def spmv_t(rowptr, col, wgt, y, ncols):
     """x = R^T y by fp64 atomics, returned in y's dtype -- for callers without the transposed arrays (LOSResponse holds
     them and uses ``spmv``); order-dependent in the last bit."""

@@ -40,6 +40,8 @@ for _name in ("selection_operators", "transpose_operator", "outer_product_operat
               "domain_tuple_field_inserter"):
     LAYOUT["operators." + _name] = "selection_operators"
 LAYOUT["operators.normal_operators"] = "correlated_fields"
+LAYOUT["operators.linear_interpolation"] = "sampling_operators"
+LAYOUT["operators.regridding_operator"] = "sampling_operators"
 
 
 class _Alias(types.ModuleType):
