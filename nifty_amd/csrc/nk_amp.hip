@@ -108,7 +108,9 @@ __device__ __forceinline__ void amp_store_sums(const double (&v)[NV] /* valid in
 // geo layout: rel[nb] | sc[nb] | mult[nb] | delta[nb]
 // hyp layout: lm_fluct, ls_fluct, lm_flex, ls_flex, lm_asp, ls_asp, lm_zm, ls_zm, slope_mean, slope_sigma, V
 // lat layout: xi_asp, xi_flex, xi_fluct, xi_slope, xi_zm, spectrum[2][nb-2]
-// state layout: [0] flex [1] asp [2] fluct [3] zm [4] slope [5] S [6] last ; 16: spec[nb] | ahat[nb] | tmp[nb] | tmp2[nb]
+// state layout: [0] flex [1] asp [2] fluct [3] zm [4] slope [5] S [6] last ... [14] ticket (the scalars: see below);
+//               16: spec[nb] | ahat[nb] | tmp[nb] | nb unused; 16 + 4 nb: segs | part (amp_segs, amp_part): at most
+//               3 (nb / 1024 + 2) + 2 (nb / 256 + 1) <= 4 nb doubles for nb >= 3, inside the 8 nb + 16 of include/niftyk.h
 struct Hyper {
   double flex, asp, fluct, zm, slope;
 };
@@ -217,6 +219,13 @@ struct AmpPtrs {
   const double *rel, *sc, *mult, *delta;
   double *spec, *ahat, *tmp, *segs, *part;
 };
+__device__ __forceinline__ double* amp_segs(int nb, double* state) {
+  return state + 16 + 4 * (size_t)nb;  // 3 doubles per scan workgroup (<= (nb - 2) / 1024 + 1, <= MAXG)
+}
+__device__ __forceinline__ double* amp_part(int nb, double* state) {
+  int ng = (nb + 1023) / 1024 + 1;
+  return amp_segs(nb, state) + 3 * (ng > MAXG ? MAXG : ng);  // 2 doubles per workgroup of the reducing launch (<= nb / 256 + 1, <= MAXG)
+}
 __device__ __forceinline__ AmpPtrs amp_ptrs(int nb, const double* geo, double* state) {
   AmpPtrs a;
   a.rel = geo;
@@ -226,9 +235,8 @@ __device__ __forceinline__ AmpPtrs amp_ptrs(int nb, const double* geo, double* s
   a.spec = state + 16;
   a.ahat = a.spec + nb;
   a.tmp = a.ahat + nb;
-  a.segs = state + 16 + 4 * (size_t)nb;  // 3 doubles per scan workgroup (<= (nb - 2) / 1024 + 1, <= MAXG)
-  int ng = (nb + 1023) / 1024 + 1;
-  a.part = a.segs + 3 * (ng > MAXG ? MAXG : ng);  // 2 doubles per workgroup of the reducing launch (<= nb / 256 + 1, <= MAXG)
+  a.segs = amp_segs(nb, state);
+  a.part = amp_part(nb, state);
   return a;
 }
 
@@ -397,7 +405,7 @@ __global__ void __launch_bounds__(AMP_THREADS) k_vjp_red1(int nb, const double* 
   __syncthreads();
   const double v[2] = {V * s1, s2};
   double* const dst[2] = {state + 8, state + 9};
-  amp_store_sums<2>(v, amp_ptrs(nb, nullptr, state).part, dst, sh_d, amp_ticket(state));
+  amp_store_sums<2>(v, amp_part(nb, state), dst, sh_d, amp_ticket(state));
 }
 
 __global__ void __launch_bounds__(AMP_THREADS) k_vjp_red2(int nb, const double* __restrict__ geo, const double* __restrict__ hyp,
