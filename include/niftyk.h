@@ -417,7 +417,13 @@ int nk_octant_expand_k2(int ndim, const int64_t* shape, const double* table, con
  * 64-bit FIXED POINT (quantum 2^(e-44), 2^e >= *w8max): integer additions commute, so the bin sums are the same bits on
  * every run at the speed of the atomics; rounding <= 2.8e-14 * max |w8| per point (used while a workgroup's share of the
  * octant stays far below the 2^18-point overflow bound: up to ~1100^3; larger grids fall back to the next case).  NULL: floating-point LDS atomics (sums
- * differ in the last bit from run to run).  NK_SCATTER_FP_ATOMICS=1 (environment) forces the latter. */
+ * differ in the last bit from run to run).  NK_SCATTER_FP_ATOMICS=1 (environment) forces the latter.
+ * Contract of the fixed-point sums: for a finite *w8max > 0 that is >= max |w8|, e = max(frexp exponent of *w8max, -979) and
+ * q = 2^(e-44); every contribution is v / q rounded to the nearest integer (ties to even), the 16 first-axis splits
+ * (a mod 16) are summed as integers, each converted to a double once and added in split order.  A bin of m points is
+ * within m q / 2 of the sum of its 16 exact split sums' doubles -- for EVERY such maximum down to the subnormal ones (below
+ * 2^-979 the quantum stays 2^-1023; it is never derived from an overflowed 2^(44-e)).  *w8max == 0 gives zeros, a NaN or
+ * an infinity gives NaN in every bin. */
 int nk_octant_scatter_k2(int ndim, const int64_t* shape, const double* w8, const int32_t* pidx, const int32_t* bin_k2,
                          int64_t nb, double* scratch, double* abar, const double* w8max, void* stream);
 /* nk_segment_sum: dst[s] (+)= sum_{rowptr[s] <= i < rowptr[s+1]} src[perm[i]] -- the same scatter-add for a static index map

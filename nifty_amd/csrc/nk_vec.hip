@@ -1783,6 +1783,10 @@ __global__ void __launch_bounds__(256)
   const bool finite = gmax <= 1.79769313486231570815e308;  // false for NaN and +inf
   int e = 0;
   if (finite && gmax > 0.0) (void)frexp(gmax, &e);
+  // maxima below 2^-979 (subnormal ones included) keep the quantum 2^-1023: 2^(44 - e) would be +inf beyond, and
+  // nk_fixed_rn(+-inf) is a finite integer -- wrong bins that look like results.  2^-1023 and every integer multiple of it
+  // are exact doubles, so the clamp costs no rounding of its own
+  e = max(e, -979);
   const double scale = ldexp(1.0, 44 - e), inv = ldexp(1.0, e - 44);
   unsigned int mine = 0u;
   const int klo = bin_k2[bin0];
