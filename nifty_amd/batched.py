@@ -190,19 +190,15 @@ def _vjp(model, scr, points, ws, w2s, scale, outs_xi, addends, dot_outs=None):
     fuses = []
     w8s, abars, latbars = scr["w8"][:count], scr["abar"][:count], scr["latbar"][:count]
     for m, pt in enumerate(points):
-        lp = pt.lp
+        lane = scr.sets[m]  # (owns abar and w8: the filler of the lane, with the lane as its scratch set)
         f = model._fuse()
         f.pro, f.in_ = L.PRO_PLAIN, ws[m].data_ptr()
         if w2s is not None:
             f.pro, f.in2 = L.PRO_MUL, w2s[m].data_ptr()
-        f.epi, f.out, f.scale = L.EPI_VJP, outs_xi[m].data_ptr(), model.h_dvol * scale
-        f.pidx, f.amp, f.xi = model.pidx.data_ptr(), lp.amp.data_ptr(), lp.x.xi.data_ptr()
-        f.afield = B.ptr(lp.afield)
         vec, fac = addends[m] if addends[m] is not None else (None, 0.0)
-        f.addend, f.addend_scale, f.accumulate = (B.ptr(vec.xi) if (vec is not None and fac) else None), fac, 0
-        if dot_outs is not None and dot_outs[m] is not None:
-            f.value = dot_outs[m].data_ptr()
-        f.abar, f.w8 = abars[m].data_ptr(), w8s[m].data_ptr()
+        # (no check of dot_outs against the addends here, unlike engine.FusedModel._vjp: the callers pair them)
+        lane._epi_vjp(f, pt.lp, lane, outs_xi[m], scale, vec.xi if (vec is not None and fac) else None, fac,
+                      dot_out=None if dot_outs is None else dot_outs[m])
         fuses.append(f)
     _transform(model, fuses, scr)
     rowsum(model.seg_plan, w8s, abars, dtype_code=L.NK_F64)
@@ -222,11 +218,9 @@ def metric(model, scr, points, ds, outs, scale, addends, dot_outs=None):
     _expand(model, damps, dafields)
     fuses = []
     for m, pt in enumerate(points):
-        lp, d = pt.lp, ds[m]
+        lp = pt.lp
         f = model._fuse()
-        f.pro, f.in_, f.in2 = L.PRO_AMP_JVP, d.xi.data_ptr(), lp.x.xi.data_ptr()
-        f.pidx, f.amp, f.damp = model.pidx.data_ptr(), lp.amp.data_ptr(), damps[m].data_ptr()
-        f.afield, f.dafield = B.ptr(lp.afield), dafields[m].data_ptr()
+        model._pro_amp_jvp(f, lp, ds[m], scr.sets[m])  # (a lane's damp / dafield: the member's scratch set)
         if model.response is not None:
             f.epi, f.out, f.mul, f.mul_scalar = L.EPI_MUL, tmps[m].data_ptr(), lp.gp.data_ptr(), 1.0
         else:
@@ -365,16 +359,12 @@ def _linearize(model, scr, xs, w):
         fuses = []
         for m, (lp, x) in enumerate(zip(lps, xs)):
             f = model._fuse()
-            f.pro, f.in_, f.pidx, f.amp = L.PRO_AMP, x.xi.data_ptr(), model.pidx.data_ptr(), lp.amp.data_ptr()
-            f.afield = lp.afield.data_ptr()
+            model._pro_amp(f, x.xi, lp.amp, lp.afield)
             if not model.const_mid:
                 lp.mid = torch.empty(model.shape, dtype=model.tdtype, device=dev)
             else:
                 lp.mid_scalar = model.icov_scalar
-            f.epi, f.out, f.out2 = L.EPI_LIKELIHOOD, tmps[m].data_ptr(), B.ptr(lp.mid)
-            f.offset, f.lh_kind, f.nonlin = model.offset_mean, model.lh_kind, model.nonlin
-            f.data, f.icov, f.icov_scalar = model.data.data_ptr(), B.ptr(model.icov_field), model.icov_scalar
-            f.value = lhvals[m].data_ptr()
+            model._epi_likelihood(f, tmps[m], lp.mid, lhvals[m])
             fuses.append(f)
         if model.wide:
             raise RuntimeError("batched evaluation: fp32 models with the wide forward transform run unbatched")
@@ -397,7 +387,8 @@ def _linearize(model, scr, xs, w):
 def _response_residual(model, lp, x, tmp, lhval):
     """engine.FusedModel._linearize_response up to the signal-space residual: fills lp.gp (and lp.wd), the likelihood value
     -> lhval, returns R^T (dE/dmu) on the grid."""
-    model._forward_nonlin(lp, x, tmp)
+    lp.gp = torch.empty(model.shape, dtype=model.tdtype, device=model.device)
+    model._forward_nonlin(x.xi, lp.amp, lp.afield, tmp, lp.gp)
     mu = model.response.times(tmp)
     if model.lh_kind == L.LH_GAUSS:
         r = B.axpby(1.0, mu, -1.0, model.data)

@@ -349,6 +349,16 @@ class _Dest:
         self.xi, self.accumulate, self.carries, self.small, self.after, self.fresh = xi, accumulate, carries, small, after, fresh
 
 
+class _ScratchSet:
+    """What ONE metric application scribbles on between its launches (FusedModel.scratch_sets): the amplitude tangent as a
+    table and as an octant field, the octant sums of the VJP epilogue with their maximum, the transform's workspace."""
+
+    __slots__ = ("damp", "dafield", "w8", "w8max", "workspace")
+
+    def __init__(self, damp, dafield, w8, w8max, workspace):
+        self.damp, self.dafield, self.w8, self.w8max, self.workspace = damp, dafield, w8, w8max, workspace
+
+
 class _PairTree:
     """Bookkeeping of a sum over this rank's samples in the order of parallel.pair_tree (utilities.py:349-414) WITHOUT
     keeping the terms: a binary counter of partial sums.  Sample i joins the partial sums that end at i -- one per
@@ -647,18 +657,119 @@ class FusedModel:
         f.field_octant = 1 if self.octant_vjp else 0
         return f
 
+    # -- the prologues and epilogues of struct nk_fuse: every record of this module and of batched.py is filled here ---------
+    def _pro_amp(self, f, xi, amp, afield):
+        """prologue a[pindex] xi"""
+        f.pro, f.in_, f.pidx, f.amp = L.PRO_AMP, xi.data_ptr(), self.pidx.data_ptr(), amp.data_ptr()
+        f.afield = B.ptr(afield)
+
+    def _pro_amp_jvp(self, f, lp, d, sc, damp_t=None, cg_direction=None, pipe=None):
+        """prologue a dxi + da xi at lp, the tangent da from the scratch set `sc` (`_amp_tangent`; damp_t: what that returned);
+        cg_direction, pipe: see lh_metric_accumulate."""
+        f.pro, f.in_, f.in2 = L.PRO_AMP_JVP, d.xi.data_ptr(), lp.x.xi.data_ptr()
+        f.pidx, f.amp, f.damp = self.pidx.data_ptr(), lp.amp.data_ptr(), sc.damp.data_ptr()
+        f.afield = B.ptr(lp.afield)
+        if damp_t is not None:
+            f.pidx_octant, f.dampT = self.pidx8.data_ptr(), damp_t.data_ptr()
+        else:
+            f.dafield = sc.dafield.data_ptr()
+        if cg_direction is not None:
+            f.cg_r, f.cg_scal = cg_direction[0].xi.data_ptr(), cg_direction[1].scal.data_ptr()
+        if pipe is not None:
+            f.pipe_chunks = pipe[0]
+            f.pipe_wait = None if pipe[1] is None else ctypes.cast(pipe[1], ctypes.c_void_p)
+            f.pipe_record = None if pipe[2] is None else ctypes.cast(pipe[2], ctypes.c_void_p)
+
+    def _epi_nonlin(self, f, out, out2):
+        f.epi, f.out, f.out2, f.offset, f.nonlin = L.EPI_NONLIN, out.data_ptr(), B.ptr(out2), self.offset_mean, self.nonlin
+
+    def _epi_likelihood(self, f, out, mid, lhval):
+        """epilogue dE/ds -> out, the s-space metric weight -> mid (unless it is a constant), the likelihood energy -> lhval"""
+        f.epi, f.out, f.out2 = L.EPI_LIKELIHOOD, out.data_ptr(), B.ptr(mid)
+        f.offset, f.lh_kind, f.nonlin = self.offset_mean, self.lh_kind, self.nonlin
+        f.data, f.icov, f.icov_scalar, f.value = self.data.data_ptr(), B.ptr(self.icov_field), self.icov_scalar, lhval.data_ptr()
+
+    def _epi_vjp(self, f, lp, sc, out_xi, scale, addend, addend_scale, accumulate=False, carries=(), dot_out=None):
+        """epilogue out_xi (+)= a t + addend_scale * addend (+ carries), t = scale * dvol_h * (the transform), with the sums
+        xi t per bin on their way to self.abar: through the octant sums of the scratch set `sc`, the full-grid array wfull or
+        the private copies of abar (what `_vjp` does after the launch).  dot_out: += sum addend * out_xi."""
+        f.epi, f.out, f.scale = L.EPI_VJP, out_xi.data_ptr(), self.h_dvol * scale
+        f.pidx, f.amp, f.xi = self.pidx.data_ptr(), lp.amp.data_ptr(), lp.x.xi.data_ptr()
+        f.afield = B.ptr(lp.afield)
+        f.addend, f.addend_scale, f.accumulate = B.ptr(addend), addend_scale, 1 if accumulate else 0
+        if len(carries) > 2:
+            raise ValueError("the VJP epilogue takes at most two carried partial sums")
+        f.carry1, f.carry2 = (B.ptr(c) for c in (tuple(carries) + (None, None))[:2])
+        if dot_out is not None:
+            f.value = dot_out.data_ptr()
+        if self.octant_vjp:
+            # the final pass stores one merged sum per octant point; `_bin_sums` reduces them into the bins
+            f.abar, f.w8 = self.abar.data_ptr(), sc.w8.data_ptr()
+            if self.scatter_fixed_point:  # max |w8| of this launch: the scale of the fixed-point shell scatter
+                f.w8max = sc.w8max.data_ptr()
+        elif self.full_plan is not None:
+            f.abar, f.wfull = self.abar.data_ptr(), self.wfull.data_ptr()
+        else:
+            f.abar, f.abar_copies, f.abar_stride = self.abar_priv.data_ptr(), self.abar_copies, self.abar_stride
+
+    def _amp_tangent(self, lp, d, sc, gather=False):
+        """The amplitude tangent of d at lp into the scratch set: the table sc.damp and its octant field sc.dafield -- or,
+        gather, no field: returns the table in the field dtype for the first pass to gather from (NK_DA_GATHER)."""
+        L.check(L.load().nk_amp_jvp(self.nb, self.geo.data_ptr(), self.hyp.data_ptr(), lp.x.small.data_ptr(),
+                                    lp.state.data_ptr(), d.small.data_ptr(), sc.damp.data_ptr(), B._stream()), "nk_amp_jvp")
+        if gather:
+            return sc.damp if self.tdtype == torch.float64 else sc.damp.to(self.tdtype)
+        self._amp_field(sc.damp, out=sc.dafield)
+
+    def _bin_sums(self, sc):
+        """self.abar <- the octant sums sc.w8 of a finished VJP epilogue, bin by bin"""
+        shp = (ctypes.c_int64 * len(self.shape))(*self.shape)
+        if self.bin_k2 is not None:
+            L.check(L.load().nk_octant_scatter_k2(len(self.shape), shp, sc.w8.data_ptr(), self.pidx.data_ptr(),
+                                                  self.bin_k2.data_ptr(), self.nb, self.scatter_scratch.data_ptr(),
+                                                  self.abar.data_ptr(),
+                                                  sc.w8max.data_ptr() if self.scatter_fixed_point else 0, B._stream()),
+                    "nk_octant_scatter_k2")
+        elif self.seg_plan is not None:
+            rowptr, perm, lanes = self.seg_plan
+            L.check(L.load().nk_csr_rowsum(self.nb, rowptr.data_ptr(), perm.data_ptr(), 0, sc.w8.data_ptr(),
+                                           self.abar.data_ptr(), L.NK_F64, lanes, B._stream()), "nk_csr_rowsum")
+        else:
+            self.abar.zero_()
+            L.check(L.load().nk_octant_scatter(len(self.shape), shp, sc.w8.data_ptr(), self.pidx.data_ptr(),
+                                               self.abar.data_ptr(), self.merge_swapped, B._stream()),
+                    "nk_octant_scatter")
+
+    def scratch_sets(self, count):
+        """`count` scratch sets of a metric application: the model's own arrays, then further ones allocated on first use
+        (sample B of a pair, the members of a group)."""
+        more = self.__dict__.setdefault("_more_sets", [])
+        while 1 + len(more) < count:
+            more.append(_ScratchSet(torch.empty_like(self.damp), torch.empty_like(self.dafield), torch.empty_like(self.w8),
+                                    torch.zeros_like(self.w8max), torch.empty_like(self.plan.workspace)))
+        return [_ScratchSet(self.damp, self.dafield, self.w8, self.w8max, self.plan.workspace)] + more[:count - 1]
+
+    def release_group_buffers(self):
+        """Hand the scratch sets beyond the pair's back to the allocator (the sampling phase is over: the KL that follows
+        holds one position per sample and needs the room)."""
+        del self.__dict__.get("_more_sets", [])[1:]
+
+    def _forward_nonlin(self, xi, amp, afield, out, out2):
+        """nonlin(s) -> out and, optionally, nonlin'(s) -> out2 for s = offset + HT(a xi): one transform with the pointwise
+        epilogue."""
+        f = self._fuse()
+        self._pro_amp(f, xi, amp, afield)
+        self._epi_nonlin(f, out, out2)
+        B.hartley_fused(self.plan, f)
+        self._count("transforms", 1)
+
     def signal(self, x, want_derivative=False):
         """nonlin(offset + HT(a xi)) as a device tensor (and optionally nonlin')."""
         amp, _ = self._amp_forward(x.small)
-        f = self._fuse()
-        f.pro, f.in_, f.pidx, f.amp = L.PRO_AMP, x.xi.data_ptr(), self.pidx.data_ptr(), amp.data_ptr()
         afield = self._amp_field(amp)
-        f.afield = afield.data_ptr()
         out = torch.empty(self.shape, dtype=self.tdtype, device=self.device)
         d = torch.empty_like(out) if want_derivative else None
-        f.epi, f.out, f.out2, f.offset, f.nonlin = L.EPI_NONLIN, out.data_ptr(), B.ptr(d), self.offset_mean, self.nonlin
-        B.hartley_fused(self.plan, f)
-        self._count("transforms", 1)
+        self._forward_nonlin(x.xi, amp, afield, out, d)
         return (out, d) if want_derivative else out
 
     def _vjp(self, lp, w, scale, addend, addend_scale, accumulate, out_xi, dot_out=None, w2=None, sandwich=None, carries=()):
@@ -668,17 +779,9 @@ class FusedModel:
         sandwich = (fill_prologue, scale_first, mid, mid_scalar): t = scale * HT(mid_scalar * mid . scale_first *
         HT(prologue)) through nk_hartley_sandwich instead (w is ignored)."""
         f = self._fuse()
-
-        def run(f):
-            if sandwich is None:
-                B.hartley_fused(self.plan, f)
-            else:
-                B.hartley_sandwich(self.plan, f, sandwich[1])
-
-        if dot_out is not None:
-            if addend is None or not self.octant_vjp:
-                raise ValueError("dot_out needs an addend and the register-resident transform pipeline")
-            f.value = dot_out.data_ptr()
+        sc = self.scratch_sets(1)[0]
+        if dot_out is not None and (addend is None or not self.octant_vjp):
+            raise ValueError("dot_out needs an addend and the register-resident transform pipeline")
         if sandwich is not None:
             sandwich[0](f)
             f.mul, f.mul_scalar = B.ptr(sandwich[2]), sandwich[3]
@@ -686,45 +789,20 @@ class FusedModel:
             f.pro, f.in_ = L.PRO_PLAIN, w.data_ptr()
             if w2 is not None:
                 f.pro, f.in2 = L.PRO_MUL, w2.data_ptr()
-        f.epi, f.out, f.scale = L.EPI_VJP, out_xi.data_ptr(), self.h_dvol * scale
-        f.pidx, f.amp, f.xi = self.pidx.data_ptr(), lp.amp.data_ptr(), lp.x.xi.data_ptr()
-        f.afield = B.ptr(lp.afield)
-        f.addend, f.addend_scale, f.accumulate = B.ptr(addend), addend_scale, 1 if accumulate else 0
-        if len(carries) > 2:
-            raise ValueError("the VJP epilogue takes at most two carried partial sums")
-        f.carry1, f.carry2 = (B.ptr(c) for c in (tuple(carries) + (None, None))[:2])
+        self._epi_vjp(f, lp, sc, out_xi, scale, addend, addend_scale, accumulate, carries, dot_out)
+        if not self.octant_vjp and self.full_plan is None:
+            self.abar_priv.zero_()
+        if sandwich is None:
+            B.hartley_fused(self.plan, f)
+        else:
+            B.hartley_sandwich(self.plan, f, sandwich[1])
         if self.octant_vjp:
-            # the final pass stores one merged sum per octant point; nk_octant_scatter reduces them into the bins
-            f.abar, f.w8 = self.abar.data_ptr(), self.w8.data_ptr()
-            if self.scatter_fixed_point:  # max |w8| of this launch: the scale of the fixed-point shell scatter
-                f.w8max = self.w8max.data_ptr()
-            run(f)
-            shp = (ctypes.c_int64 * len(self.shape))(*self.shape)
-            if self.bin_k2 is not None:
-                L.check(L.load().nk_octant_scatter_k2(len(self.shape), shp, self.w8.data_ptr(), self.pidx.data_ptr(),
-                                                      self.bin_k2.data_ptr(), self.nb, self.scatter_scratch.data_ptr(),
-                                                      self.abar.data_ptr(),
-                                                      self.w8max.data_ptr() if self.scatter_fixed_point else 0, B._stream()),
-                        "nk_octant_scatter_k2")
-            elif self.seg_plan is not None:
-                rowptr, perm, lanes = self.seg_plan
-                L.check(L.load().nk_csr_rowsum(self.nb, rowptr.data_ptr(), perm.data_ptr(), 0, self.w8.data_ptr(),
-                                               self.abar.data_ptr(), L.NK_F64, lanes, B._stream()), "nk_csr_rowsum")
-            else:
-                self.abar.zero_()
-                L.check(L.load().nk_octant_scatter(len(self.shape), shp, self.w8.data_ptr(), self.pidx.data_ptr(),
-                                                   self.abar.data_ptr(), self.merge_swapped, B._stream()),
-                        "nk_octant_scatter")
+            self._bin_sums(sc)
         elif self.full_plan is not None:
-            f.abar, f.wfull = self.abar.data_ptr(), self.wfull.data_ptr()
-            run(f)
             rowptr, perm, lanes = self.full_plan
             L.check(L.load().nk_csr_rowsum(self.nb, rowptr.data_ptr(), perm.data_ptr(), 0, self.wfull.data_ptr(),
                                            self.abar.data_ptr(), L.NK_F64, lanes, B._stream()), "nk_csr_rowsum")
         else:
-            f.abar, f.abar_copies, f.abar_stride = self.abar_priv.data_ptr(), self.abar_copies, self.abar_stride
-            self.abar_priv.zero_()
-            run(f)
             L.check(L.load().nk_fold_copies(self.nb, self.abar_copies, self.abar_stride, self.abar_priv.data_ptr(),
                                             self.abar.data_ptr(), B._stream()), "nk_fold_copies")
         self._count("transforms", 1 if sandwich is None else 2)
@@ -767,16 +845,13 @@ class FusedModel:
         if self.response is not None:
             return self._linearize_response(lp, x, grad_acc if dest is None else dest, w, value, lhval, want_gradient)
         f = self._fuse()
-        f.pro, f.in_, f.pidx, f.amp = L.PRO_AMP, x.xi.data_ptr(), self.pidx.data_ptr(), lp.amp.data_ptr()
-        f.afield = lp.afield.data_ptr()
+        self._pro_amp(f, x.xi, lp.amp, lp.afield)
         gs = self.tmp
         if not self.const_mid:
             lp.mid = torch.empty(self.shape, dtype=self.tdtype, device=self.device)
         else:
             lp.mid_scalar = self.icov_scalar
-        f.epi, f.out, f.out2 = L.EPI_LIKELIHOOD, gs.data_ptr(), B.ptr(lp.mid)
-        f.offset, f.lh_kind, f.nonlin = self.offset_mean, self.lh_kind, self.nonlin
-        f.data, f.icov, f.icov_scalar, f.value = self.data.data_ptr(), B.ptr(self.icov_field), self.icov_scalar, lhval.data_ptr()
+        self._epi_likelihood(f, gs, lp.mid, lhval)
         if self.wide:
             # fp32 arrays at both ends of an fp64 transform (see __init__): a(k) xi(k) with the fp64 amplitude
             plan64, afield64, dense64 = self._wide_buffers()
@@ -820,8 +895,7 @@ class FusedModel:
                 for name in self._SCRATCH:
                     t = getattr(self, name)
                     setattr(lane, name, None if t is None else torch.zeros_like(t))
-                lane._wide_state = lane._pair = None
-                lane._lanes = [lane]
+                lane._wide_state, lane._more_sets, lane._lanes = None, [], [lane]
                 lane.stream = torch.cuda.Stream(device=self.device)
                 made.append(lane)
         return made[:count]
@@ -884,16 +958,6 @@ class FusedModel:
         return lp
 
     # -- models with a linear response between the signal and the data (BASELINE config 4) -------------------------
-    def _forward_nonlin(self, lp, x, g_out):
-        """g(s) -> g_out and g'(s) -> lp.gp for s = offset + HT(a xi): one transform with the pointwise epilogue."""
-        f = self._fuse()
-        f.pro, f.in_, f.pidx, f.amp = L.PRO_AMP, x.xi.data_ptr(), self.pidx.data_ptr(), lp.amp.data_ptr()
-        f.afield = lp.afield.data_ptr()
-        lp.gp = torch.empty(self.shape, dtype=self.tdtype, device=self.device)
-        f.epi, f.out, f.out2, f.offset, f.nonlin = L.EPI_NONLIN, g_out.data_ptr(), lp.gp.data_ptr(), self.offset_mean, self.nonlin
-        B.hartley_fused(self.plan, f)
-        self._count("transforms", 1)
-
     def _forward_nonlin_wide(self, lp, x):
         """g(s) as an fp64 tensor for a model with fp32 fields (`wide_response`): the transform runs on the fp64 plan of the
         grid with xi widened and the fp64 amplitude (octant field where both plans have the register-resident pipeline, the
@@ -912,9 +976,8 @@ class FusedModel:
         gp = torch.empty_like(g)
         f = self._fuse()
         f.field_octant = 1 if octant else 0
-        f.pro, f.in_, f.pidx, f.amp = L.PRO_AMP, xi64.data_ptr(), self.pidx.data_ptr(), lp.amp.data_ptr()
-        f.afield = self._amp_field(lp.amp, out=afield64, dense=dense64).data_ptr() if octant else None
-        f.epi, f.out, f.out2, f.offset, f.nonlin = L.EPI_NONLIN, g.data_ptr(), gp.data_ptr(), self.offset_mean, self.nonlin
+        self._pro_amp(f, xi64, lp.amp, self._amp_field(lp.amp, out=afield64, dense=dense64) if octant else None)
+        self._epi_nonlin(f, g, gp)
         B.hartley_fused(plan64, f)
         self._count("transforms", 1)
         lp.gp = gp.to(self.tdtype)
@@ -933,7 +996,8 @@ class FusedModel:
             mu = self.response.times(self._forward_nonlin_wide(lp, x))
             data, icov, wide = self._data64, self._icov64, torch.float64
         else:
-            self._forward_nonlin(lp, x, self.tmp)
+            lp.gp = torch.empty(self.shape, dtype=self.tdtype, device=self.device)
+            self._forward_nonlin(x.xi, lp.amp, lp.afield, self.tmp, lp.gp)
             mu = self.response.times(self.tmp)
             data, icov, wide = self.data, self.icov_field, self.tdtype
         if self.lh_kind == L.LH_GAUSS:
@@ -955,18 +1019,20 @@ class FusedModel:
         gs = self.response.adjoint(ir, self.shape)
         return self._finish_linearize(lp, x, gs, lp.gp, grad_acc, w, value, lhval)
 
-    def _jvp_response(self, lp, d, cg_direction=None):
-        """R (g'(s) . J_cf d): latent tangent -> data space (one transform, one row-sum launch)."""
-        L.check(L.load().nk_amp_jvp(self.nb, self.geo.data_ptr(), self.hyp.data_ptr(), lp.x.small.data_ptr(),
-                                    lp.state.data_ptr(), d.small.data_ptr(), self.damp.data_ptr(), B._stream()), "nk_amp_jvp")
-        self._amp_field(self.damp, out=self.dafield)
+    def _jvp_field(self, lp, d, sc, mul, mul_scalar, out):
+        """out <- mul_scalar * mul . dvol_h HT(a dxi + da xi) with the tangent da in the scratch set (`_amp_tangent`): one
+        transform with the pointwise epilogue."""
         f = self._fuse()
-        f.pro, f.in_, f.in2 = L.PRO_AMP_JVP, d.xi.data_ptr(), lp.x.xi.data_ptr()
-        f.pidx, f.amp, f.damp = self.pidx.data_ptr(), lp.amp.data_ptr(), self.damp.data_ptr()
-        f.afield, f.dafield = B.ptr(lp.afield), self.dafield.data_ptr()
-        f.epi, f.out, f.mul, f.mul_scalar = L.EPI_MUL, self.tmp.data_ptr(), lp.gp.data_ptr(), 1.0
+        self._pro_amp_jvp(f, lp, d, sc)
+        f.epi, f.out, f.mul, f.mul_scalar = L.EPI_MUL, out.data_ptr(), B.ptr(mul), mul_scalar
         B.hartley_fused(self.plan, f)
         self._count("transforms", 1)
+
+    def _jvp_response(self, lp, d, cg_direction=None):
+        """R (g'(s) . J_cf d): latent tangent -> data space (one transform, one row-sum launch)."""
+        sc = self.scratch_sets(1)[0]
+        self._amp_tangent(lp, d, sc)
+        self._jvp_field(lp, d, sc, lp.gp, 1.0, self.tmp)
         return self.response.times(self.tmp)
 
     def lh_metric_accumulate(self, lp, d, out, scale, first, identity=0.0, dot_out=None, cg_direction=None, pipe=None,
@@ -992,61 +1058,31 @@ class FusedModel:
             self._vjp(lp, wsig, scale, avec.xi if afac else None, afac, dot_out=dot_out, w2=lp.gp, **where)
             self._finish_metric(lp, avec, out, first, afac, dest)
             return
-        L.check(L.load().nk_amp_jvp(self.nb, self.geo.data_ptr(), self.hyp.data_ptr(), lp.x.small.data_ptr(),
-                                    lp.state.data_ptr(), d.small.data_ptr(), self.damp.data_ptr(), B._stream()), "nk_amp_jvp")
         # da[pindex] is expanded to an octant field once per application (1/8 of the gathers, 0.72 ms at 1024^3 fp32).
         # NK_DA_GATHER=1 lets the sandwich's first pass gather it from the table through the octant bin index instead:
         # measured 3.3 -> 8.9 ms for that pass (dependent gathers in a latency-bound row kernel) -- not the default
+        # (this route only: the pair and the group always expand)
         gather_da = self.sandwich and self.pidx8 is not None and os.environ.get("NK_DA_GATHER", "0") == "1"
-        if gather_da:
-            damp_t = self.damp if self.tdtype == torch.float64 else self.damp.to(self.tdtype)
-        else:
-            self._amp_field(self.damp, out=self.dafield)
-
-        def jvp_prologue(f):
-            f.pro, f.in_, f.in2 = L.PRO_AMP_JVP, d.xi.data_ptr(), lp.x.xi.data_ptr()
-            f.pidx, f.amp, f.damp = self.pidx.data_ptr(), lp.amp.data_ptr(), self.damp.data_ptr()
-            f.afield = B.ptr(lp.afield)
-            if gather_da:
-                f.pidx_octant, f.dampT = self.pidx8.data_ptr(), damp_t.data_ptr()
-            else:
-                f.dafield = self.dafield.data_ptr()
-            if cg_direction is not None:
-                f.cg_r, f.cg_scal = cg_direction[0].xi.data_ptr(), cg_direction[1].scal.data_ptr()
-            if pipe is not None:
-                f.pipe_chunks = pipe[0]
-                f.pipe_wait = None if pipe[1] is None else ctypes.cast(pipe[1], ctypes.c_void_p)
-                f.pipe_record = None if pipe[2] is None else ctypes.cast(pipe[2], ctypes.c_void_p)
-
+        sc = self.scratch_sets(1)[0]
+        damp_t = self._amp_tangent(lp, d, sc, gather_da)
         if pipe is not None and not self.sandwich:
             raise ValueError("slab pipelining needs the sandwich pipeline")
         if self.sandwich:
             # H D H in five passes: the position-space field between the transforms never exists (nk_fft3.h)
-            self._vjp(lp, None, scale, avec.xi if afac else None, afac, dot_out=dot_out,
-                      sandwich=(jvp_prologue, self.h_dvol, lp.mid, lp.mid_scalar), **where)
+            self._vjp(lp, None, scale, avec.xi if afac else None, afac, dot_out=dot_out, **where,
+                      sandwich=(lambda f: self._pro_amp_jvp(f, lp, d, sc, damp_t, cg_direction, pipe), self.h_dvol, lp.mid,
+                                lp.mid_scalar))
             if cg_direction is not None:
                 cg_direction[1].roll()
         else:
-            f = self._fuse()
-            jvp_prologue(f)
-            f.epi, f.out, f.mul, f.mul_scalar = L.EPI_MUL, self.tmp.data_ptr(), B.ptr(lp.mid), lp.mid_scalar
-            B.hartley_fused(self.plan, f)
+            self._jvp_field(lp, d, sc, lp.mid, lp.mid_scalar, self.tmp)
             self._vjp(lp, self.tmp, scale, avec.xi if afac else None, afac, dot_out=dot_out, **where)
-            self._count("transforms", 1)
         self._finish_metric(lp, avec, out, first, afac, dest)
 
     def pair_ready(self):
         """True when two samples' metric applications can share a final-pass launch (lh_metric_accumulate_pair)."""
         return bool(self.sandwich and self.octant_vjp and self.response is None and self.bin_k2 is not None
                     and len(self.shape) == 3 and self.const_mid and os.environ.get("NK_PAIR_FINAL", "1") != "0")
-
-    def _pair_buffers(self):
-        """Second set of the per-application scratch arrays (sample B of a pair), allocated on first use."""
-        if getattr(self, "_pair", None) is None:
-            self._pair = dict(damp=torch.empty_like(self.damp), dafield=torch.empty_like(self.dafield),
-                              w8=torch.empty_like(self.w8), w8max=torch.zeros_like(self.w8max),
-                              workspace=torch.empty_like(self.plan.workspace))
-        return self._pair
 
     def lh_metric_accumulate_pair(self, lpa, lpb, d, out, scale, first, identity=0.0, dot_out=None, cg_direction=None,
                                   dests=None, identity_first=0.0):
@@ -1059,51 +1095,29 @@ class FusedModel:
         pairwise sum sits on the first sample)."""
         if cg_direction is not None and not self.fused_direction:
             raise ValueError("cg_direction needs the sandwich pipeline (FusedModel.fused_direction)")
-        pb = self._pair_buffers()
-        lib = L.load()
-        fuses = []
+        sets = self.scratch_sets(2)
         if dests is None:
             dests = (_Dest(out.xi, accumulate=not first), _Dest(out.xi, accumulate=True))
-        for lp, damp, dafield, w8, w8max, dest in ((lpa, self.damp, self.dafield, self.w8, self.w8max, dests[0]),
-                                                   (lpb, pb["damp"], pb["dafield"], pb["w8"], pb["w8max"], dests[1])):
-            L.check(lib.nk_amp_jvp(self.nb, self.geo.data_ptr(), self.hyp.data_ptr(), lp.x.small.data_ptr(), lp.state.data_ptr(),
-                                   d.small.data_ptr(), damp.data_ptr(), B._stream()), "nk_amp_jvp")
-            self._amp_field(damp, out=dafield)
+        # (sample, scratch set, destination, multiple of d its epilogue adds, direction update, curvature dot, first onto out)
+        members = ((lpa, sets[0], dests[0], identity_first, cg_direction, None, first),
+                   (lpb, sets[1], dests[1], identity, None, dot_out if identity else None, False))
+        fuses = []
+        for lp, sc, dest, ident, direction, dot, _ in members:
+            self._amp_tangent(lp, d, sc)
             f = self._fuse()
-            f.pro, f.in_, f.in2 = L.PRO_AMP_JVP, d.xi.data_ptr(), lp.x.xi.data_ptr()
-            f.pidx, f.amp, f.damp = self.pidx.data_ptr(), lp.amp.data_ptr(), damp.data_ptr()
-            f.afield, f.dafield = B.ptr(lp.afield), dafield.data_ptr()
+            self._pro_amp_jvp(f, lp, d, sc, cg_direction=direction)
             f.mul, f.mul_scalar = B.ptr(lp.mid), lp.mid_scalar
-            f.epi, f.out, f.scale = L.EPI_VJP, dest.xi.data_ptr(), self.h_dvol * scale
-            f.xi = lp.x.xi.data_ptr()
-            f.addend, f.addend_scale, f.accumulate = None, 0.0, 1 if dest.accumulate else 0
-            f.carry1, f.carry2 = (B.ptr(c) for c in (tuple(dest.carries) + (None, None))[:2])
-            f.abar, f.w8 = self.abar.data_ptr(), w8.data_ptr()
-            if self.scatter_fixed_point:
-                f.w8max = w8max.data_ptr()
+            self._epi_vjp(f, lp, sc, dest.xi, scale, d.xi if ident else None, ident, dest.accumulate, dest.carries, dot)
             fuses.append(f)
-        if cg_direction is not None:
-            fuses[0].cg_r, fuses[0].cg_scal = cg_direction[0].xi.data_ptr(), cg_direction[1].scal.data_ptr()
-        if identity_first:
-            fuses[0].addend, fuses[0].addend_scale = d.xi.data_ptr(), identity_first
-        if identity:
-            fuses[1].addend, fuses[1].addend_scale = d.xi.data_ptr(), identity
-            if dot_out is not None:
-                fuses[1].value = dot_out.data_ptr()
-        elif dot_out is not None:
+        if dot_out is not None and not identity:  # (this route's own message: its addend can only be the identity term)
             raise ValueError("dot_out needs the identity term (the addend of the epilogue)")
-        B.hartley_sandwich_pair(self.plan, fuses[0], fuses[1], self.h_dvol, pb["workspace"])
+        B.hartley_sandwich_pair(self.plan, fuses[0], fuses[1], self.h_dvol, sets[1].workspace)
         _PairTree.settle(dests[1])
         if cg_direction is not None:
             cg_direction[1].roll()
         self._count("transforms", 4)
-        shp = (ctypes.c_int64 * len(self.shape))(*self.shape)
-        for lp, w8, w8max, is_first, dest, ident in ((lpa, self.w8, self.w8max, first, dests[0], identity_first),
-                                                     (lpb, pb["w8"], pb["w8max"], False, dests[1], identity)):
-            L.check(lib.nk_octant_scatter_k2(len(self.shape), shp, w8.data_ptr(), self.pidx.data_ptr(), self.bin_k2.data_ptr(),
-                                             self.nb, self.scatter_scratch.data_ptr(), self.abar.data_ptr(),
-                                             w8max.data_ptr() if self.scatter_fixed_point else 0, B._stream()),
-                    "nk_octant_scatter_k2")
+        for lp, sc, dest, ident, _, _, is_first in members:
+            self._bin_sums(sc)
             self._finish_metric(lp, d, out, is_first, ident, dest)
 
     def group_ready(self):
@@ -1112,23 +1126,6 @@ class FusedModel:
         return bool(self.pair_ready() and self.fused_direction and os.environ.get("NK_GROUP", "1") != "0"
                     and os.environ.get("NK_DA_GATHER", "0") != "1")
 
-    def _group_buffers(self, count):
-        """`count` sets of the per-application scratch arrays: the model's own, the pair's second set (_pair_buffers), then
-        further ones allocated on first use."""
-        own = dict(damp=self.damp, dafield=self.dafield, w8=self.w8, w8max=self.w8max, workspace=self.plan.workspace)
-        sets = [own, self._pair_buffers()] if count > 1 else [own]
-        more = self.__dict__.setdefault("_group_more", [])
-        while len(sets) + len(more) < count:
-            more.append(dict(damp=torch.empty_like(self.damp), dafield=torch.empty_like(self.dafield),
-                             w8=torch.empty_like(self.w8), w8max=torch.zeros_like(self.w8max),
-                             workspace=torch.empty_like(self.plan.workspace)))
-        return (sets + more)[:count]
-
-    def release_group_buffers(self):
-        """Hand the scratch sets beyond the pair's back to the allocator (the sampling phase is over: the KL that follows
-        holds one position per sample and needs the room)."""
-        self.__dict__.pop("_group_more", None)
-
     def lh_metric_group(self, lp, jobs):
         """[J^T M J d + identity * d  (or + factor * vector)] for up to L.MAX_GROUP directions at ONE linearisation point --
         the sampling solves of an MGVI iteration -- as one nk_hartley_sandwich_group call: the first passes, which all read
@@ -1136,45 +1133,28 @@ class FusedModel:
         `addend` = (vector, factor), `dot_out`, `cg_direction` (all or none) as in lh_metric_accumulate, `lp` = a linearisation
         point of its own (samples of a KL that share the direction instead); per job the kernels,
         the arithmetic and the bits are those of lh_metric_accumulate(lp, d, out, 1.0, True, ...).  Returns the outputs."""
-        lib = L.load()
-        bufs = self._group_buffers(len(jobs))
+        sets = self.scratch_sets(len(jobs))
         fuses, outs, adds = [], [], []
         points = [job.get("lp", lp) for job in jobs]
-        for job, buf, lp in zip(jobs, bufs, points):
+        for job, sc, lp in zip(jobs, sets, points):
             d = job["d"]
             avec, afac = (d, job.get("identity", 0.0)) if job.get("addend") is None else job["addend"]
             out = LatentVec(torch.empty_like(d.xi), None)
-            L.check(lib.nk_amp_jvp(self.nb, self.geo.data_ptr(), self.hyp.data_ptr(), lp.x.small.data_ptr(), lp.state.data_ptr(),
-                                   d.small.data_ptr(), buf["damp"].data_ptr(), B._stream()), "nk_amp_jvp")
-            self._amp_field(buf["damp"], out=buf["dafield"])
+            self._amp_tangent(lp, d, sc)
             f = self._fuse()
-            f.pro, f.in_, f.in2 = L.PRO_AMP_JVP, d.xi.data_ptr(), lp.x.xi.data_ptr()
-            f.pidx, f.amp, f.damp = self.pidx.data_ptr(), lp.amp.data_ptr(), buf["damp"].data_ptr()
-            f.afield, f.dafield = B.ptr(lp.afield), buf["dafield"].data_ptr()
-            if job.get("cg_direction") is not None:
-                f.cg_r, f.cg_scal = job["cg_direction"][0].xi.data_ptr(), job["cg_direction"][1].scal.data_ptr()
+            self._pro_amp_jvp(f, lp, d, sc, cg_direction=job.get("cg_direction"))
             f.mul, f.mul_scalar = B.ptr(lp.mid), lp.mid_scalar
-            f.epi, f.out, f.scale = L.EPI_VJP, out.xi.data_ptr(), self.h_dvol
-            f.xi = lp.x.xi.data_ptr()
-            f.addend, f.addend_scale, f.accumulate = B.ptr(avec.xi if afac else None), afac, 0
-            if job.get("dot_out") is not None:
-                if not afac:
-                    raise ValueError("dot_out needs an addend and the register-resident transform pipeline")
-                f.value = job["dot_out"].data_ptr()
-            f.abar, f.w8 = self.abar.data_ptr(), buf["w8"].data_ptr()
-            if self.scatter_fixed_point:
-                f.w8max = buf["w8max"].data_ptr()
+            if job.get("dot_out") is not None and not afac:  # (the single route's message, raised member by member)
+                raise ValueError("dot_out needs an addend and the register-resident transform pipeline")
+            self._epi_vjp(f, lp, sc, out.xi, 1.0, avec.xi if afac else None, afac, dot_out=job.get("dot_out"))
             fuses.append(f)
             outs.append(out)
             adds.append((avec, afac))
-        B.hartley_sandwich_group(self.plan, fuses, self.h_dvol, [buf["workspace"] for buf in bufs])
-        shp = (ctypes.c_int64 * len(self.shape))(*self.shape)
-        for job, buf, out, (avec, afac), lp in zip(jobs, bufs, outs, adds, points):
+        B.hartley_sandwich_group(self.plan, fuses, self.h_dvol, [sc.workspace for sc in sets])
+        # (the members share self.abar: bin sums, then the amplitude VJP, member by member)
+        for job, sc, out, (avec, afac), lp in zip(jobs, sets, outs, adds, points):
             self._count("transforms", 2)
-            L.check(lib.nk_octant_scatter_k2(len(self.shape), shp, buf["w8"].data_ptr(), self.pidx.data_ptr(), self.bin_k2.data_ptr(),
-                                             self.nb, self.scatter_scratch.data_ptr(), self.abar.data_ptr(),
-                                             buf["w8max"].data_ptr() if self.scatter_fixed_point else 0, B._stream()),
-                    "nk_octant_scatter_k2")
+            self._bin_sums(sc)
             if job.get("cg_direction") is not None:
                 job["cg_direction"][1].roll()
             self._finish_metric(lp, avec, out, True, afac, _Dest(out.xi, accumulate=False))
@@ -1219,7 +1199,8 @@ class FusedModel:
         lp.afield = self._amp_field(lp.amp)
         if self.response is not None:
             # f = N^{-1/2} mu or 2 sqrt(mu) on the data space; J_f = diag(tfd) R diag(g') J_cf
-            self._forward_nonlin(lp, x, self.tmp)
+            lp.gp = torch.empty(self.shape, dtype=self.tdtype, device=self.device)
+            self._forward_nonlin(x.xi, lp.amp, lp.afield, self.tmp, lp.gp)
             mu = self.response.times(self.tmp)
             if self.lh_kind == L.LH_GAUSS:
                 lp.tfd = math.sqrt(self.icov_scalar) if self.icov_field is None else B.pointwise("sqrt", self.icov_field)
@@ -1228,14 +1209,9 @@ class FusedModel:
                 rt = B.pointwise("sqrt", mu)
                 lp.f, lp.tfd = B.axpby(2.0, rt), B.pointwise("reciprocal", rt)
             return lp
-        f = self._fuse()
-        f.pro, f.in_, f.pidx, f.amp = L.PRO_AMP, x.xi.data_ptr(), self.pidx.data_ptr(), lp.amp.data_ptr()
-        f.afield = lp.afield.data_ptr()
         g = torch.empty(self.shape, dtype=self.tdtype, device=self.device)
         gp = torch.empty_like(g)
-        f.epi, f.out, f.out2, f.offset, f.nonlin = L.EPI_NONLIN, g.data_ptr(), gp.data_ptr(), self.offset_mean, self.nonlin
-        B.hartley_fused(self.plan, f)
-        self._count("transforms", 1)
+        self._forward_nonlin(x.xi, lp.amp, lp.afield, g, gp)
         if self.lh_kind == L.LH_GAUSS:
             if self.icov_field is None:
                 tw = math.sqrt(self.icov_scalar)
@@ -1253,18 +1229,10 @@ class FusedModel:
         if self.response is not None:
             u = self._jvp_response(lp, d)
             return B.axpby(lp.tfd, u, out=out) if np.isscalar(lp.tfd) else B.binary(L.OP_MUL, u, lp.tfd, out=out)
-        L.check(L.load().nk_amp_jvp(self.nb, self.geo.data_ptr(), self.hyp.data_ptr(), lp.x.small.data_ptr(),
-                                    lp.state.data_ptr(), d.small.data_ptr(), self.damp.data_ptr(), B._stream()), "nk_amp_jvp")
-        f = self._fuse()
-        f.pro, f.in_, f.in2 = L.PRO_AMP_JVP, d.xi.data_ptr(), lp.x.xi.data_ptr()
-        f.pidx, f.amp, f.damp = self.pidx.data_ptr(), lp.amp.data_ptr(), self.damp.data_ptr()
-        f.afield = B.ptr(lp.afield)
-        self._amp_field(self.damp, out=self.dafield)
-        f.dafield = self.dafield.data_ptr()
+        sc = self.scratch_sets(1)[0]
+        self._amp_tangent(lp, d, sc)
         out = torch.empty(self.shape, dtype=self.tdtype, device=self.device) if out is None else out
-        f.epi, f.out, f.mul, f.mul_scalar = L.EPI_MUL, out.data_ptr(), lp.tf.data_ptr(), 1.0
-        B.hartley_fused(self.plan, f)
-        self._count("transforms", 1)
+        self._jvp_field(lp, d, sc, lp.tf, 1.0, out)
         return out
 
     def vjp_data(self, lp, w, addend=None):

@@ -80,11 +80,11 @@ def class8_single(model, lp, ds, rs, count):
 def class8_group(model, lp, ds, rs, count):
     jobs, keep = class8_jobs(model, ds, rs, count)
     qs = model.lh_metric_group(lp, jobs)
-    bufs = model._group_buffers(count)
+    bufs = model.scratch_sets(count)
     out = {}
     for m, (q, (d, ws, dot), buf) in enumerate(zip(qs, keep, bufs)):
         out.update({f"out{m}": q.xi, f"small{m}": q.small, f"in{m}": d.xi, f"dot{m}": dot.clone(), f"scal{m}": ws.scal.clone(),
-                    f"w8_{m}": buf["w8"].clone(), f"w8max{m}": buf["w8max"].clone()})
+                    f"w8_{m}": buf.w8.clone(), f"w8max{m}": buf.w8max.clone()})
     return out
 
 
@@ -99,10 +99,10 @@ def class5_single(model, lps, d, count):
 
 def class5_group(model, lps, d, count):
     qs = model.lh_metric_group(lps[0], [dict(d=d, addend=(lps[m].x, -1.0), lp=lps[m]) for m in range(count)])
-    bufs = model._group_buffers(count)
+    bufs = model.scratch_sets(count)
     out = {}
     for m, (q, buf) in enumerate(zip(qs, bufs)):
-        out.update({f"out{m}": q.xi, f"small{m}": q.small, f"w8_{m}": buf["w8"].clone(), f"w8max{m}": buf["w8max"].clone()})
+        out.update({f"out{m}": q.xi, f"small{m}": q.small, f"w8_{m}": buf.w8.clone(), f"w8max{m}": buf.w8max.clone()})
     return out
 
 

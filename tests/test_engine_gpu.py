@@ -343,7 +343,7 @@ def test_pair_final_pass_is_bit_identical(shape, dtype):
         w8_b = model.w8.clone()
         model.lh_metric_accumulate_pair(lps[0], lps[1], d, par, 0.125, first)
         assert torch.equal(seq.xi, par.xi) and torch.equal(seq.small, par.small)
-        assert torch.equal(w8_b, model._pair["w8"])
+        assert torch.equal(w8_b, model.scratch_sets(2)[1].w8)
     # the KL metric over five samples: first and last single (direction update / identity + curvature), the middle ones paired
     res = [x - xs[0] for x in xs]
     kl = FusedKL(model, xs[0], res, [False] * 5)
