@@ -426,6 +426,19 @@ int nk_octant_expand_k2(int ndim, const int64_t* shape, const double* table, con
  * an infinity gives NaN in every bin. */
 int nk_octant_scatter_k2(int ndim, const int64_t* shape, const double* w8, const int32_t* pidx, const int32_t* bin_k2,
                          int64_t nb, double* scratch, double* abar, const double* w8max, void* stream);
+/* The same reduction for the n = 1..4 members of a launch group whose octant arrays are alive together: w8[n], scratch[n],
+ * abar[n], w8max[n] are HOST arrays of device pointers (scratch[g]: >= 16*(nb+32) doubles of member g's own, abar[g]: nb
+ * doubles; no two members may share a scratch or an output array, the same w8 may serve several members).  With a scale for
+ * every member (and within the fixed-point bound above, held for the grouped kernel's shell count as well) the shell walk --
+ * square roots, row addresses, the pidx stream -- runs ONCE per launch and every point is added to each member's own copy of
+ * the shell with that member's own scale.  Contract: abar[g] holds the BITS of nk_octant_scatter_k2 on member g alone -- same
+ * integer per point, integer sums per (bin, first-axis split), one conversion, the same fold; the shell width of the grouped
+ * kernel and how it packs members into launches (NK_SHELL_GROUP_BINS / _THREADS / _MAX, environment: developer sweeps) do
+ * not enter the result.  The zero / NaN / infinity rules apply member by member.  Without a scale for every member (w8max or
+ * one of its entries NULL), with NK_SCATTER_FP_ATOMICS=1 or beyond the bound the members run as n nk_octant_scatter_k2 calls. */
+int nk_octant_scatter_k2_group(int ndim, const int64_t* shape, int n, const double* const* w8, const int32_t* pidx,
+                               const int32_t* bin_k2, int64_t nb, double* const* scratch, double* const* abar,
+                               const double* const* w8max, void* stream);
 /* nk_segment_sum: dst[s] (+)= sum_{rowptr[s] <= i < rowptr[s+1]} src[perm[i]] -- the same scatter-add for a static index map
  * given as a bin-sorted permutation of the source points (rowptr: int32[nseg+1], perm: int32[rowptr[nseg]]): one thread per
  * bin, fixed summation order, no atomics.  The engine uses it for the quadrant sums of 2-D grids. */

@@ -112,6 +112,7 @@ SIGNATURES = {
     "nk_octant_expand_k2": (_i, [_i, ctypes.POINTER(_i64), _vp, _vp, _i64, _vp, _vp, _i, _vp, _vp]),
     "nk_segment_sum": (_i, [_i64, _vp, _vp, _vp, _vp, _i, _vp]),
     "nk_octant_scatter_k2": (_i, [_i, ctypes.POINTER(_i64), _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "nk_octant_scatter_k2_group": (_i, [_i, ctypes.POINTER(_i64), _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "nk_plan_octant_vjp": (_i, [_vp]),
     "nk_fold_copies": (_i, [_i64, _i, _i64, _vp, _vp, _vp]),
     "nk_cumsum": (_i, [_i64, _vp, _vp, _i, _i, _vp]),

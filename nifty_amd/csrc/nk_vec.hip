@@ -1882,6 +1882,216 @@ extern "C" int nk_octant_scatter_k2(int ndim, const int64_t* shape, const double
   return nk_fold_copies(nb, NK_SHELL_SPLITS, pstride, scratch, abar, stream);
 }
 
+// ---- the fixed-point shell scatter for the members of a launch group: ONE walk, G octant arrays ----------------------------
+// klo / khi, b_lo / b_hi, the two roots per line, the row offsets and the pidx load depend on the grid and the shell alone;
+// per member a point costs its w8 load, the product with that member's scale, nk_fixed_rn and one LDS atomic into the member's
+// own copy of the shell (acc[g][bin - bin0]).  Per member the BITS are those of k_octant_scatter_k2_fx: the integer a point
+// adds is the same expression of the same operands, integer additions commute, and the partial of (bin, split) is the sum over
+// the points of that bin with a = s (mod NK_SHELL_SPLITS) however bins are packed into workgroups and lines into trips --
+// neither the shell width BINS nor the lines per step THREADS / 16 enters the result (a narrower shell only tightens the
+// overflow bound).  Members g >= n are inactive (a group of three in the kernel of four).
+// The kernel lives on loads in flight like the single one, so the workgroup grows with its LDS: 1024^3, ms per launch against
+// 0.66 per single (tools/gpu_scatter_group_probe.py, profiles/r12_scatter_group_probe.jsonl) --
+//   shell 4096, threads 256 / 512 / 1024:  pair 1.48 / 1.02 / 1.27   three 3.40 / 2.02 / 1.53   four 3.79 / 2.28 / 1.86
+//   shell 2048, threads 256 / 512 / 1024:  pair 1.40 / 1.61 / 2.19   three 2.78 / 1.99 / 2.41   four 3.02 / 2.53 / 2.82
+// (a narrower shell halves the run per line, ~5 points on 16 lanes, and doubles the index work the grouping is there to share)
+#ifndef NK_SHELL_GROUP_BINS
+#define NK_SHELL_GROUP_BINS 4096
+#endif
+#ifndef NK_SHELL_GROUP_THREADS2
+#define NK_SHELL_GROUP_THREADS2 512   // pairs: 64 KiB of LDS, two workgroups per CU
+#endif
+#ifndef NK_SHELL_GROUP_THREADS4
+#define NK_SHELL_GROUP_THREADS4 1024  // three or four members: 128 KiB of LDS, one workgroup per CU
+#endif
+#ifndef NK_SHELL_GROUP_MAX
+#define NK_SHELL_GROUP_MAX 4  // largest group that goes out as one launch (2: groups of four go as two pairs)
+#endif
+#define NK_SCATTER_GROUP_LIMIT 4
+
+template <int G>
+struct NkShellGroup {
+  const double* w8[G];
+  const double* w8max[G];
+  double* partial[G];
+};
+
+template <int G, int BINS, int THREADS>
+__global__ void __launch_bounds__(THREADS)
+    k_octant_scatter_k2_fx_g(NkOct o, int n, NkShellGroup<G> m, const int32_t* __restrict__ pidx,
+                             const int32_t* __restrict__ bin_k2, int nb, int64_t pstride) {
+  __shared__ unsigned long long acc[G * BINS];
+  __shared__ unsigned int npoints;
+  const int j = blockIdx.x / NK_SHELL_SPLITS, s = blockIdx.x % NK_SHELL_SPLITS;
+  const int bin0 = j * BINS;
+  const int nbin = min(BINS, nb - bin0);
+  for (int i = threadIdx.x; i < G * BINS; i += THREADS) acc[i] = 0ull;
+  if (threadIdx.x == 0) npoints = 0u;
+  __syncthreads();
+  // per member: scale, clamp and the non-finite rule of k_octant_scatter_k2_fx
+  double scale[G], inv[G];
+  bool finite[G];
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const double gmax = g < n ? *m.w8max[g] : 0.0;
+    finite[g] = gmax <= 1.79769313486231570815e308;  // false for NaN and +inf
+    int e = 0;
+    if (finite[g] && gmax > 0.0) (void)frexp(gmax, &e);
+    e = max(e, -979);
+    scale[g] = ldexp(1.0, 44 - e), inv[g] = ldexp(1.0, e - 44);
+  }
+  unsigned int mine = 0u;  // points, not point-members: the count is the same for every member
+  const int klo = bin_k2[bin0];
+  const int khi = bin0 + BINS < nb ? bin_k2[bin0 + BINS] : 0x7fffffff;
+  const int hc2 = (o.Ch - 1) * (o.Ch - 1);
+  constexpr int LINES = THREADS / 16, NU = G == 4 ? NK_SHELL_NU / 2 : NK_SHELL_NU * 3 / 4;  // (G NU = 12 or 16 w8 loads in flight per lane)
+  const int grp = threadIdx.x >> 4, l16 = threadIdx.x & 15;
+  const bool last = khi == 0x7fffffff;
+  for (int a = s; a < o.Ah; a += NK_SHELL_SPLITS) {
+    const int ra = a * a;
+    if (ra >= khi) break;
+    const int b_hi = last ? o.Mh : min(o.Mh, nk_isqrt_ceil(khi - ra));  // b^2 < khi - ra
+    const int b_lo = nk_isqrt_ceil(klo - hc2 - ra);                      // b^2 + hc2 >= klo - ra
+    for (int b0 = b_lo + grp; b0 < b_hi; b0 += LINES * NU) {
+      int cc[NU], ce[NU];
+      int64_t wo[NU];  // the row of line u in every member's octant array
+      const int32_t* pl[NU];
+      double v[G][NU];
+      int32_t pb[NU];
+      const int64_t wo0 = ((int64_t)a * o.Mh + b0) * o.Ch;
+      const int32_t* pl0 = pidx + ((int64_t)a * o.M + b0) * o.NL;
+      const int64_t wstep = (int64_t)LINES * o.Ch, pstep = (int64_t)LINES * o.NL;
+      int r2 = ra + b0 * b0, dr2 = 2 * LINES * b0 + LINES * LINES;  // r2(b + LINES) = r2(b) + 2 LINES b + LINES^2
+#pragma unroll
+      for (int u = 0; u < NU; ++u) {
+        const int b = b0 + u * LINES;
+        const bool on = b < b_hi;
+        cc[u] = nk_isqrt_ceil(klo - r2) + l16;
+        ce[u] = on ? (last ? o.Ch : min(o.Ch, nk_isqrt_ceil(khi - r2))) : 0;
+        wo[u] = wo0 + u * wstep;
+        pl[u] = pl0 + u * pstep;
+        const bool in = cc[u] < ce[u];
+        pb[u] = in ? pl[u][cc[u]] : bin0;
+#pragma unroll
+        for (int g = 0; g < G; ++g) v[g][u] = (in && g < n) ? m.w8[g][wo[u] + cc[u]] : 0.0;
+        r2 += dr2;
+        dr2 += 2 * LINES * LINES;
+      }
+#pragma unroll
+      for (int u = 0; u < NU; ++u)
+        if (cc[u] < ce[u]) {
+#pragma unroll
+          for (int g = 0; g < G; ++g)
+            if (g < n) atomicAdd(&acc[g * BINS + pb[u] - bin0], nk_fixed_rn(v[g][u] * scale[g]));
+          ++mine;
+        }
+      // rare: runs longer than 16 points
+#pragma unroll
+      for (int u = 0; u < NU; ++u)
+        for (int c = cc[u] + 16; c < ce[u]; c += 16) {
+          const int bin = pl[u][c] - bin0;
+#pragma unroll
+          for (int g = 0; g < G; ++g)
+            if (g < n) atomicAdd(&acc[g * BINS + bin], nk_fixed_rn(m.w8[g][wo[u] + c] * scale[g]));
+          ++mine;
+        }
+    }
+  }
+  atomicAdd(&npoints, mine);
+  __syncthreads();
+  const bool few = npoints < (1u << 18);  // the overflow guard of k_octant_scatter_k2_fx
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    if (g >= n) break;
+    const bool ok = finite[g] && few;
+    double* dst = m.partial[g] + (int64_t)s * pstride + bin0;
+    for (int i = threadIdx.x; i < nbin; i += THREADS)
+      dst[i] = ok ? (double)(long long)acc[g * BINS + i] * inv[g] : __longlong_as_double(0x7ff8000000000000LL);
+  }
+}
+
+template <int G, int BINS, int THREADS>
+static void nk_launch_shell_group(const NkOct& o, int n, const NkShellGroup<G>& m, const int32_t* pidx, const int32_t* bin_k2,
+                                  int64_t nb, int64_t pstride, hipStream_t st) {
+  const int64_t shells = (nb + BINS - 1) / BINS;
+  hipLaunchKernelGGL((k_octant_scatter_k2_fx_g<G, BINS, THREADS>), dim3((unsigned)(shells * NK_SHELL_SPLITS)), dim3(THREADS), 0,
+                     st, o, n, m, pidx, bin_k2, (int)nb, pstride);
+}
+
+template <int G>
+static int nk_shell_group_launch(const NkOct& o, int n, const double* const* w8, const double* const* w8max,
+                                 double* const* scratch, const int32_t* pidx, const int32_t* bin_k2, int64_t nb, int64_t pstride,
+                                 int bins, int threads, hipStream_t st) {
+  NkShellGroup<G> m;
+  for (int g = 0; g < G; ++g) {
+    const int k = g < n ? g : 0;  // (inactive members are never dereferenced)
+    m.w8[g] = w8[k], m.w8max[g] = w8max[k], m.partial[g] = scratch[k];
+  }
+#define NK_SHELL_GROUP_CASE(B, T) \
+  if (bins == B && threads == T) nk_launch_shell_group<G, B, T>(o, n, m, pidx, bin_k2, nb, pstride, st); else
+  NK_SHELL_GROUP_CASE(4096, 512) NK_SHELL_GROUP_CASE(4096, 1024) NK_SHELL_GROUP_CASE(4096, 256)
+  NK_SHELL_GROUP_CASE(2048, 512) NK_SHELL_GROUP_CASE(2048, 1024) NK_SHELL_GROUP_CASE(2048, 256)
+  return nk_set_error(NK_ERR_INVALID, "nk_octant_scatter_k2_group: NK_SHELL_GROUP_BINS is 2048 or 4096, NK_SHELL_GROUP_THREADS 0, 256, 512 or 1024");
+#undef NK_SHELL_GROUP_CASE
+  return nk_check_launch("k_octant_scatter_k2_fx_g");
+}
+
+extern "C" int nk_octant_scatter_k2_group(int ndim, const int64_t* shape, int n, const double* const* w8, const int32_t* pidx,
+                                          const int32_t* bin_k2, int64_t nb, double* const* scratch, double* const* abar,
+                                          const double* const* w8max, void* stream) {
+  NkOct o;
+  int rc = nk_make_oct(ndim, shape, o);
+  if (rc != NK_OK) return rc;
+  if (n < 1 || n > NK_SCATTER_GROUP_LIMIT) return nk_set_error(NK_ERR_INVALID, "nk_octant_scatter_k2_group: 1 <= n <= 4");
+  if (!w8 || !pidx || !bin_k2 || !scratch || !abar || nb < 1 || nb > 0x7fffffff)
+    return nk_set_error(NK_ERR_INVALID, "nk_octant_scatter_k2_group: bad argument");
+  bool scaled = w8max != nullptr;
+  for (int g = 0; g < n; ++g) {
+    if (!w8[g] || !scratch[g] || !abar[g]) return nk_set_error(NK_ERR_INVALID, "nk_octant_scatter_k2_group: null member array");
+    for (int h = 0; h < g; ++h)
+      if (scratch[h] == scratch[g] || abar[h] == abar[g])
+        return nk_set_error(NK_ERR_INVALID, "nk_octant_scatter_k2_group: members share a scratch or an output array");
+    scaled = scaled && w8max[g] != nullptr;
+  }
+  if ((int64_t)(o.Ah - 1) * (o.Ah - 1) + (int64_t)(o.Mh - 1) * (o.Mh - 1) + (int64_t)(o.Ch - 1) * (o.Ch - 1) >= (1 << 24))
+    return nk_set_error(NK_ERR_UNSUPPORTED, "nk_octant_scatter_k2_group: k^2 range too large");
+  static const int fp_atomics = nk_vec_env_int("NK_SCATTER_FP_ATOMICS", 0);
+  // developer sweeps (tools/gpu_scatter_group_probe.py): shell width, workgroup size, largest group in one launch
+  static const int bins = nk_vec_env_int("NK_SHELL_GROUP_BINS", NK_SHELL_GROUP_BINS);
+  static const int threads_env = nk_vec_env_int("NK_SHELL_GROUP_THREADS", 0);  // (0: the defaults per group size)
+  static const int gmax = nk_vec_env_int("NK_SHELL_GROUP_MAX", NK_SHELL_GROUP_MAX);
+  // the overflow bound of the fixed-point sums with the grouped kernel's shell count -- and the single kernel's, so that a
+  // member never takes the fixed-point route here and the floating-point one alone
+  const int64_t points = (int64_t)o.Ah * o.Mh * o.Ch / NK_SHELL_SPLITS;
+  const int64_t shells_g = (nb + (bins > 0 ? bins : NK_SHELL_GROUP_BINS) - 1) / (bins > 0 ? bins : NK_SHELL_GROUP_BINS);
+  const int64_t shells_1 = (nb + NK_SHELL_BINS - 1) / NK_SHELL_BINS;
+  const bool fixed = scaled && !fp_atomics && points < ((int64_t)1 << 16) * shells_g && points < ((int64_t)1 << 16) * shells_1;
+  const int64_t pstride = (nb + 31) / 32 * 32;
+  for (int g0 = 0; g0 < n;) {
+    // members [g0, g0 + take) in one launch: no grouped floating-point kernel, groups of three as four with one inactive
+    // member or as a pair and a single (NK_SHELL_GROUP_MAX)
+    const int left = n - g0;
+    const int take = !fixed || left == 1 || gmax < 2 ? 1 : (gmax >= 4 ? left : 2);
+    if (take == 1) {
+      rc = nk_octant_scatter_k2(ndim, shape, w8[g0], pidx, bin_k2, nb, scratch[g0], abar[g0], w8max ? w8max[g0] : nullptr, stream);
+      if (rc != NK_OK) return rc;
+    } else {
+      const int threads = threads_env > 0 ? threads_env : (take == 2 ? NK_SHELL_GROUP_THREADS2 : NK_SHELL_GROUP_THREADS4);
+      rc = take == 2 ? nk_shell_group_launch<2>(o, take, w8 + g0, w8max + g0, scratch + g0, pidx, bin_k2, nb, pstride, bins, threads,
+                                                (hipStream_t)stream)
+                     : nk_shell_group_launch<4>(o, take, w8 + g0, w8max + g0, scratch + g0, pidx, bin_k2, nb, pstride, bins, threads,
+                                                (hipStream_t)stream);
+      if (rc != NK_OK) return rc;
+      for (int g = g0; g < g0 + take; ++g) {
+        rc = nk_fold_copies(nb, NK_SHELL_SPLITS, pstride, scratch[g], abar[g], stream);
+        if (rc != NK_OK) return rc;
+      }
+    }
+    g0 += take;
+  }
+  return NK_OK;
+}
+
 // ---- sparse response (LOSResponse, reference library/los_response.py:144-253): CSR with int32 columns and
 //      float32 weights (the reference stores float32 weights too, :196), fp64 accumulation ------------------
 // y[i] = sum_j (wgt ? wgt[j] : 1) * x[col[j]]  over rowptr[i] <= j < rowptr[i+1].  LANES lanes share a row (1, 4, 16 or 64):

@@ -351,12 +351,14 @@ class _Dest:
 
 class _ScratchSet:
     """What ONE metric application scribbles on between its launches (FusedModel.scratch_sets): the amplitude tangent as a
-    table and as an octant field, the octant sums of the VJP epilogue with their maximum, the transform's workspace."""
+    table and as an octant field, the octant sums of the VJP epilogue with their maximum, the transform's workspace, the bin
+    sums of the octant sums with the shell scatter's partial sums (the members of a grouped scatter each write their own)."""
 
-    __slots__ = ("damp", "dafield", "w8", "w8max", "workspace")
+    __slots__ = ("damp", "dafield", "w8", "w8max", "workspace", "abar", "scatter_scratch")
 
-    def __init__(self, damp, dafield, w8, w8max, workspace):
+    def __init__(self, damp, dafield, w8, w8max, workspace, abar, scatter_scratch):
         self.damp, self.dafield, self.w8, self.w8max, self.workspace = damp, dafield, w8, w8max, workspace
+        self.abar, self.scatter_scratch = abar, scatter_scratch
 
 
 class _PairTree:
@@ -531,6 +533,9 @@ class FusedModel:
                 self.scatter_busiest = int(torch.bincount(key.reshape(-1)).max().item())
                 self.scatter_fixed_point = self.scatter_busiest < (1 << 18)
                 del key, a_idx
+            # the members of a pair or a group reduce their octant sums in ONE shell walk (nk_octant_scatter_k2_group; the same
+            # bits member by member).  NK_GROUP_SCATTER=0: one scatter per member
+            self.group_scatter = self.scatter_fixed_point and os.environ.get("NK_GROUP_SCATTER", "1") != "0"
             self.k2_dense = self.k2_line_order = None
             if self.bin_k2 is not None and os.environ.get("NK_EXPAND_K2", "1") != "0":
                 self.k2_dense = torch.zeros(int(self.bin_k2[-1].item()) + 1, dtype=dtype, device=self.device)
@@ -740,14 +745,37 @@ class FusedModel:
                                                self.abar.data_ptr(), self.merge_swapped, B._stream()),
                     "nk_octant_scatter")
 
+    def _bin_sums_group(self, sets):
+        """sc.abar <- the octant sums sc.w8, bin by bin, for every scratch set of a finished pair or group: one shell walk
+        for all of them (`group_scatter`).  Without it: returns False and the caller runs `_bin_sums` member by member."""
+        if not self.group_scatter or len(sets) < 2:
+            return False
+        shp = (ctypes.c_int64 * len(self.shape))(*self.shape)
+
+        def ptrs(ts):
+            return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+        L.check(L.load().nk_octant_scatter_k2_group(len(self.shape), shp, len(sets), ptrs([sc.w8 for sc in sets]),
+                                                    self.pidx.data_ptr(), self.bin_k2.data_ptr(), self.nb,
+                                                    ptrs([sc.scatter_scratch for sc in sets]), ptrs([sc.abar for sc in sets]),
+                                                    ptrs([sc.w8max for sc in sets]), B._stream()),
+                "nk_octant_scatter_k2_group")
+        return True
+
     def scratch_sets(self, count):
         """`count` scratch sets of a metric application: the model's own arrays, then further ones allocated on first use
         (sample B of a pair, the members of a group)."""
         more = self.__dict__.setdefault("_more_sets", [])
         while 1 + len(more) < count:
+            # (bin sums and partial sums of its own only where members are scattered together: 16 split rows of nb doubles)
+            own = self.group_scatter
             more.append(_ScratchSet(torch.empty_like(self.damp), torch.empty_like(self.dafield), torch.empty_like(self.w8),
-                                    torch.zeros_like(self.w8max), torch.empty_like(self.plan.workspace)))
-        return [_ScratchSet(self.damp, self.dafield, self.w8, self.w8max, self.plan.workspace)] + more[:count - 1]
+                                    torch.zeros_like(self.w8max), torch.empty_like(self.plan.workspace),
+                                    torch.zeros_like(self.abar) if own else self.abar,
+                                    torch.empty(16 * (self.nb + 32), dtype=torch.float64, device=self.device) if own
+                                    else self.scatter_scratch))
+        return [_ScratchSet(self.damp, self.dafield, self.w8, self.w8max, self.plan.workspace, self.abar,
+                            self.scatter_scratch)] + more[:count - 1]
 
     def release_group_buffers(self):
         """Hand the scratch sets beyond the pair's back to the allocator (the sampling phase is over: the KL that follows
@@ -807,9 +835,11 @@ class FusedModel:
                                             self.abar.data_ptr(), B._stream()), "nk_fold_copies")
         self._count("transforms", 1 if sandwich is None else 2)
 
-    def _amp_vjp(self, lp):
+    def _amp_vjp(self, lp, abar=None):
+        """self.latbar <- the amplitude VJP of the bin sums `abar` (default: self.abar; a member of a grouped scatter: its own)"""
+        abar = self.abar if abar is None else abar
         L.check(L.load().nk_amp_vjp(self.nb, self.geo.data_ptr(), self.hyp.data_ptr(), lp.x.small.data_ptr(),
-                                    lp.state.data_ptr(), self.abar.data_ptr(), self.latbar.data_ptr(), B._stream()),
+                                    lp.state.data_ptr(), abar.data_ptr(), self.latbar.data_ptr(), B._stream()),
                 "nk_amp_vjp")
 
     def metric_point(self, x):
@@ -1116,9 +1146,11 @@ class FusedModel:
         if cg_direction is not None:
             cg_direction[1].roll()
         self._count("transforms", 4)
+        together = self._bin_sums_group(sets)
         for lp, sc, dest, ident, _, _, is_first in members:
-            self._bin_sums(sc)
-            self._finish_metric(lp, d, out, is_first, ident, dest)
+            if not together:
+                self._bin_sums(sc)
+            self._finish_metric(lp, d, out, is_first, ident, dest, abar=sc.abar if together else None)
 
     def group_ready(self):
         """True when the metric applications of several solves at one linearisation point can go out as grouped launches
@@ -1151,17 +1183,20 @@ class FusedModel:
             outs.append(out)
             adds.append((avec, afac))
         B.hartley_sandwich_group(self.plan, fuses, self.h_dvol, [sc.workspace for sc in sets])
-        # (the members share self.abar: bin sums, then the amplitude VJP, member by member)
+        # one grouped scatter into the members' own bin sums -- or (NK_GROUP_SCATTER=0) the members share self.abar: bin
+        # sums, then the amplitude VJP, member by member
+        together = self._bin_sums_group(sets)
         for job, sc, out, (avec, afac), lp in zip(jobs, sets, outs, adds, points):
             self._count("transforms", 2)
-            self._bin_sums(sc)
+            if not together:
+                self._bin_sums(sc)
             if job.get("cg_direction") is not None:
                 job["cg_direction"][1].roll()
-            self._finish_metric(lp, avec, out, True, afac, _Dest(out.xi, accumulate=False))
+            self._finish_metric(lp, avec, out, True, afac, _Dest(out.xi, accumulate=False), abar=sc.abar if together else None)
         return outs
 
-    def _finish_metric(self, lp, d, out, first, identity, dest=None):
-        self._amp_vjp(lp)
+    def _finish_metric(self, lp, d, out, first, identity, dest=None, abar=None):
+        self._amp_vjp(lp, abar)
         if dest is not None:
             _PairTree.settle(dest)
             if dest.small is not None:  # a pairwise sum over samples: the caller adds the small parts
