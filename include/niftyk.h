@@ -319,7 +319,8 @@ int nk_scatter_add(int64_t n, const void* in, const int32_t* pidx, int64_t nbins
  *            bin-sorted permutation of the source points, wgt = NULL; np.bincount / _special_add_at, utilities.py:222-246).
  * nk_spmv  : nk_csr_rowsum with lanes = 64
  * nk_spmv_t: x64[col[j]] += wgt[j] * y[i] on a caller-zeroed fp64 array (cast to the field dtype afterwards) by fp64
- *            atomics -- for callers that do not hold the transpose; order-dependent in the last bit */
+ *            atomics -- for callers that do not hold the transpose; order-dependent in the last bit.  Like nk_spmv it
+ *            takes no NULL wgt: with nrows > 0, col and wgt are both required (NK_ERR_INVALID otherwise) */
 int nk_csr_rowsum(int64_t nrows, const int64_t* rowptr, const int32_t* col, const float* wgt, const void* x, void* y,
                   int dtype, int lanes, void* stream);
 int nk_spmv(int64_t nrows, const int64_t* rowptr, const int32_t* col, const float* wgt, const void* x, void* y, int dtype,

@@ -2359,7 +2359,9 @@ extern "C" int nk_spmv(int64_t nrows, const int64_t* rowptr, const int32_t* col,
 
 extern "C" int nk_spmv_t(int64_t nrows, const int64_t* rowptr, const int32_t* col, const float* wgt, const void* y,
                          double* x, int dtype, void* stream) {
-  if (nrows < 0 || !rowptr || (nrows > 0 && (!x || !y))) return nk_set_error(NK_ERR_INVALID, "nk_spmv_t: bad argument");
+  // (no unit weights here: k_spmv_t reads wgt[j] and col[j] of every entry)
+  if (nrows < 0 || !rowptr || (nrows > 0 && (!x || !y || !col || !wgt)))
+    return nk_set_error(NK_ERR_INVALID, "nk_spmv_t: bad argument");
   if (nrows == 0) return NK_OK;
   const unsigned blocks = (unsigned)((nrows + 3) / 4);
   NK_DISPATCH_DTYPE(dtype, {
