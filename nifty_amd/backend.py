@@ -491,6 +491,14 @@ def lanes_for(nnz, nrows):
 
 
 BIN_PLAN_MAX = 1 << 28  # largest static index map that is sorted once (the sort holds ~20 bytes per point transiently)
+# applications that summed colliding indices with ``scatter_add`` because their map is beyond BIN_PLAN_MAX: their last bits
+# depend on the order of the atomics (extra._same_answer_twice asks such an application for the reference's device bar only)
+unordered_sums = 0
+
+
+def note_unordered_sum():
+    global unordered_sums
+    unordered_sums += 1
 
 
 def bin_plan(pidx, nbins):

@@ -36,6 +36,9 @@ LATENT_KEYS = ("asperity", "flexibility", "fluctuations", "loglogavgslope", "spe
 _NONLIN = {None: L.NL_ID, "": L.NL_ID, "exp": L.NL_EXP, "sigmoid": L.NL_SIGMOID}
 # grids up to this size draw the spectrum excitations of a prior sample on the device (FusedModel.draw_prior)
 SPECTRUM_DEVICE_DRAW_MAX_POINTS = int(os.environ.get("NK_SPECTRUM_DEVICE_DRAW_MAX_POINTS", str(1 << 25)))
+# the shell scatter accumulates in fixed point while its busiest (shell, first-axis index mod 16) workgroup adds fewer points
+# than this: the overflow bound of its 64-bit sums (FusedModel.scatter_fixed_point)
+SCATTER_FIXED_POINT_MAX_POINTS = 1 << 18
 
 
 def lognormal_moments(mean, sigma):
@@ -525,13 +528,17 @@ class FusedModel:
                     self.bin_k2 = torch.from_numpy(k2).to(self.device)
             # fixed-point accumulation of the shell scatter: a workgroup = (shell of 4096 bins, first-axis index mod 16) must
             # add < 2^18 points (overflow bound of the 64-bit sums) -- counted exactly here, once (a cube heuristic missed
-            # anisotropic grids); beyond the bound the floating-point LDS atomics take over
+            # anisotropic grids); beyond the bound the octant sums are added bin by bin over `seg_plan` like those of
+            # a grid without the shell structure -- a fixed order, the same bits in every run and for a launch alone, in a pair
+            # or in a group.  (The floating-point LDS atomics of the shell scatter add in an order that varies from launch to
+            # launch: the spectrum part of a result then differs in its last bits from run to run; NK_SEGMENT_SUM=0 keeps them,
+            # for A/B.)
             self.scatter_fixed_point = False
             if self.bin_k2 is not None:
                 a_idx = torch.arange(self.shape[0] // 2 + 1, device=self.device, dtype=torch.int64)
                 key = (self.pidx8.view(self.shape[0] // 2 + 1, -1) // 4096).to(torch.int64) * 16 + (a_idx % 16)[:, None]
                 self.scatter_busiest = int(torch.bincount(key.reshape(-1)).max().item())
-                self.scatter_fixed_point = self.scatter_busiest < (1 << 18)
+                self.scatter_fixed_point = self.scatter_busiest < SCATTER_FIXED_POINT_MAX_POINTS
                 del key, a_idx
             # the members of a pair or a group reduce their octant sums in ONE shell walk (nk_octant_scatter_k2_group; the same
             # bits member by member).  NK_GROUP_SCATTER=0: one scatter per member
@@ -544,7 +551,8 @@ class FusedModel:
                     a2 = torch.arange(self.shape[0] // 2 + 1, device=self.device, dtype=torch.int64) ** 2
                     b2 = torch.arange(self.shape[1] // 2 + 1, device=self.device, dtype=torch.int64) ** 2
                     self.k2_line_order = torch.argsort((a2[:, None] + b2[None, :]).reshape(-1), stable=True).to(torch.int32)
-            if self.octant_vjp and self.bin_k2 is None and os.environ.get("NK_SEGMENT_SUM", "1") != "0":
+            if (self.octant_vjp and (self.bin_k2 is None or not self.scatter_fixed_point)
+                    and os.environ.get("NK_SEGMENT_SUM", "1") != "0"):
                 self.seg_plan = B.bin_plan(self.pidx8, self.nb)
             # WIDE forward transform of value + gradient for fp32 fields (nk_fuse.io32): the reference promotes fp32
             # excitations to fp64 at their product with the fp64 amplitude and transforms in fp64
@@ -729,7 +737,7 @@ class FusedModel:
     def _bin_sums(self, sc):
         """self.abar <- the octant sums sc.w8 of a finished VJP epilogue, bin by bin"""
         shp = (ctypes.c_int64 * len(self.shape))(*self.shape)
-        if self.bin_k2 is not None:
+        if self.bin_k2 is not None and (self.scatter_fixed_point or self.seg_plan is None):
             L.check(L.load().nk_octant_scatter_k2(len(self.shape), shp, sc.w8.data_ptr(), self.pidx.data_ptr(),
                                                   self.bin_k2.data_ptr(), self.nb, self.scatter_scratch.data_ptr(),
                                                   self.abar.data_ptr(),
@@ -2036,11 +2044,13 @@ class _HostDrawAhead:
     hands out the draws of `seed` -- started at construction for the first sample, at the previous `take` for the others --
     and starts the next sample's on a worker thread (numpy fills arrays without the interpreter lock)."""
 
+    THREAD_PREFIX = "nk-draw-ahead"  # name of the worker thread: what is left of it shows in threading.enumerate()
+
     def __init__(self, model, seeds):
         from concurrent.futures import ThreadPoolExecutor
 
         self._model, self._seeds = model, list(seeds)
-        self._pool = ThreadPoolExecutor(max_workers=1)
+        self._pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix=self.THREAD_PREFIX)
         self._pending = {}
         self._start(0)
 

@@ -28,8 +28,16 @@ def assert_equal(f1, f2, *, atol=0.0, rtol=0.0):
 
 def _same_answer_twice(op, x):
     """An operator is a pure function of its input: applying it twice gives the same bits (extra.py:368-380; the device
-    reductions of libniftyk are built in a fixed order, so this holds on the GPU too)."""
-    assert_equal(op(x), op(x))
+    reductions of libniftyk are built in a fixed order, so this holds on the GPU too).  The one exception sums colliding
+    indices with atomics -- index maps beyond backend.BIN_PLAN_MAX -- and is held to the reference's bar for device results."""
+    from . import backend as B
+
+    before = B.unordered_sums
+    first, second = op(x), op(x)
+    if B.unordered_sums != before:
+        assert_allclose(first, second)
+    else:
+        assert_equal(first, second)
 
 
 def _largest_entry(f):

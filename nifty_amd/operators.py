@@ -1598,6 +1598,7 @@ class ContractionOperator(LinearOperator):
                 if isinstance(plan, tuple):
                     res = B.bin_sum(x.val.contiguous().reshape(-1), plan)
                 else:
+                    B.note_unordered_sum()
                     res = B.scatter_add(x.val.contiguous().reshape(-1), plan, nkept).to(x.val.dtype)
                 return Field(self._target, res.reshape(self._target.shape))
             return Field.scalar(x.s_sum()).at(x.device_id)
@@ -1976,6 +1977,7 @@ class DOFDistributor(LinearOperator):
             plan = self._bin_plans[key]
             if plan is not None:
                 return B.bin_sum(v.contiguous().reshape(-1), plan)
+            B.note_unordered_sum()
             bins = B.scatter_add(v.contiguous().reshape(-1), self._device_index(v.device), self._nbin)
             return bins.to(v.dtype)
         out = torch.zeros(self._nbin, dtype=torch.float64)

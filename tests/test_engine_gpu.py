@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from oracle import nifty_oracle as orc
+from tests import engine_route_cases as rc
 from tests import goldenlib as gl
 
 pytestmark = pytest.mark.gpu
@@ -154,59 +155,22 @@ def test_geovi_energy_vs_oracle(shape):
                                                ((512, 4096), "poisson", "exp")])
 @pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
 def test_engine_vs_oracle_seeded(shape, kind, nonlin, dtype):
-    """Same seeded inputs through the HIP engine and the numpy oracle; fp32 fields use fp64 accumulators."""
-    from nifty_amd.engine import FusedModel, LatentVec
+    """Same seeded inputs through the HIP engine and the numpy oracle; fp32 fields use fp64 accumulators (the body, shared with
+    the routes of tests/test_engine_routes_gpu.py: engine_route_cases.seeded_engine_vs_oracle)."""
+    def tolerances(model):
+        # (12 x 10 x 14 Poisson: 1.8e-5 -- the residual lambda - d cancels, and on 1680 points the fp32 ADJOINT transform's
+        # rounding, relative to lambda, is not averaged down; the generic Gaussian cases and every register-resident case hold 1e-5)
+        # metric application, fp32: asserted at twice the worst error measured per class on the GPU (round 6,
+        # gpurun_out/r06h/seeded_errors.txt -> profiles/r06_seeded_errors.txt): 1.4e-6 over all cases but one -- 96 x 160 x 96 with
+        # the sigmoid, 5.6e-5 PER KEY: the key is the scalar `fluctuations`, a cancelling sum over all bins that comes out at 30
+        # where `xi` reaches 2.3e4 (7e-8 of the vector's largest entry; every other key of that case <= 5e-7) -- until round 5 a
+        # blanket 2e-4 for every fp32 case
+        mtol32 = 1.2e-4 if (shape == (96, 160, 96) and nonlin == "sigmoid") else 3e-6
+        if dtype == torch.float64:
+            return 1e-10, 1e-10
+        return (1e-5 if (model.wide or kind == "gaussian") else 5e-5), mtol32
 
-    rng = np.random.default_rng(11)
-    cf = orc.CFModel(shape, None, orc.CFParams(offset_mean=1.5))
-    truth = cf.draw_latent(rng)
-    s = cf.forward(truth)
-    g, _ = orc.NONLIN[nonlin]
-    if kind == "gaussian":
-        data = g(s) + 0.1 * rng.normal(size=shape)
-        lh = orc.Likelihood("gaussian", data, icov=100.0, nonlin=nonlin)
-        model = FusedModel(shape, offset_mean=1.5, likelihood="gaussian", data=data, icov=100.0, nonlin=nonlin, dtype=dtype)
-    else:
-        data = rng.poisson(g(s)).astype(np.int64)
-        lh = orc.Likelihood("poisson", data, nonlin=nonlin)
-        model = FusedModel(shape, offset_mean=1.5, likelihood="poisson", data=data, nonlin=nonlin, dtype=dtype)
-    x = {k: 0.3 * a for k, a in cf.draw_latent(rng).items()}
-    v = cf.draw_latent(rng)
-    if dtype == torch.float32:  # identical inputs for both paths
-        x["xi"] = x["xi"].astype(np.float32).astype(np.float64)
-        v["xi"] = v["xi"].astype(np.float32).astype(np.float64)
-        if kind == "gaussian":
-            lh.data = lh.data.astype(np.float32).astype(np.float64)
-    lin = orc.Linearized(cf, lh, x)
-    val, grad = lin.value_grad()
-    mv = lin.metric(v)
-    xl, vl = LatentVec.from_dict(model, x), LatentVec.from_dict(model, v)
-    lp = model.linearize(xl)
-    # fp32 fields: value + gradient within the 1e-5 of north_star on every grid (their forward transform runs in fp64:
-    # FusedModel.wide on the register-resident pipelines, FusedModel.wide_generic on mixed-radix grids and short axes);
-    # a metric application is two fp32 transforms with a pointwise weight in between
-    if dtype == torch.float32:
-        assert model.wide or model.wide_generic
-    # (12 x 10 x 14 Poisson: 1.8e-5 -- the residual lambda - d cancels, and on 1680 points the fp32 ADJOINT transform's rounding,
-    # relative to lambda, is not averaged down; the generic Gaussian cases and every register-resident case hold 1e-5)
-    # metric application, fp32: asserted at twice the worst error measured per class on the GPU (round 6,
-    # gpurun_out/r06h/seeded_errors.txt -> profiles/r06_seeded_errors.txt): 1.4e-6 over all cases but one -- 96 x 160 x 96 with
-    # the sigmoid, 5.6e-5 PER KEY: the key is the scalar `fluctuations`, a cancelling sum over all bins that comes out at 30
-    # where `xi` reaches 2.3e4 (7e-8 of the vector's largest entry; every other key of that case <= 5e-7) -- until round 5 a
-    # blanket 2e-4 for every fp32 case
-    mtol32 = 1.2e-4 if (shape == (96, 160, 96) and nonlin == "sigmoid") else 3e-6
-    tol, mtol = (1e-10, 1e-10) if dtype == torch.float64 else (1e-5 if (model.wide or kind == "gaussian") else 5e-5, mtol32)
-    e_val = abs(float(lp.value.item()) - val) / abs(val)
-    e_grad, e_met = gl.lat_relerr(lp.grad.to_dict(), grad), gl.lat_relerr(model.metric(lp, vl).to_dict(), mv)
-    print(f"{shape} {kind} {nonlin} {dtype}: value {e_val:.1e} gradient {e_grad:.1e} metric {e_met:.1e}")
-    assert e_val < tol and e_grad < tol and e_met < mtol
-    # adjointness of the metric (reference extra.py:220-231): <u, M v> == <M u, v>
-    u = LatentVec.from_dict(model, cf.draw_latent(rng))
-    mvl = model.metric(lp, vl)
-    a = u.s_vdot(mvl)
-    b = model.metric(lp, u).s_vdot(vl)
-    # <u, M v> of two random vectors cancels to a small number: the rounding scale is |u| |M v|, not |a|
-    assert abs(a - b) < (1e-12 if dtype == torch.float64 else 2e-6) * u.norm() * mvl.norm()
+    rc.seeded_engine_vs_oracle(shape, kind, nonlin, dtype, tolerances)
 
 
 def test_engine_rejects_cpu():
@@ -264,55 +228,9 @@ def test_engine_full_size_properties(shape, kind, nonlin, dtype):
 def test_sandwich_engine_vs_oracle(shape, dtype, lh, monkeypatch):
     """Grids large enough for the five-pass sandwich (every axis >= 64, last >= 128): metric application, MGVI sample
     (CG with the fused curvature dot AND the direction update riding in the first transform pass) and KL against the
-    numpy oracle; and the same run with the fusions switched off."""
-    from nifty_amd import random
-    from nifty_amd.engine import FusedKL, FusedModel, LatentVec, draw_samples
-    from nifty_amd.minimization import AbsDeltaEnergyController
-
-    rng = np.random.default_rng(3)
-    cf = orc.CFModel(shape, None, orc.CFParams(offset_mean=1.0))
-    x = {k: 0.2 * v for k, v in cf.draw_latent(rng).items()}
-    v = cf.draw_latent(rng)
-    if lh == "poisson":
-        data = rng.poisson(np.exp(cf.forward(cf.draw_latent(rng)) * 0.3)).astype(np.int64)
-        lho = orc.Likelihood("poisson", data, nonlin="exp")
-        kw = dict(likelihood="poisson", data=data, nonlin="exp")
-    else:
-        data = cf.forward(cf.draw_latent(rng)) + 0.1 * rng.normal(size=shape)
-        lho = orc.Likelihood("gaussian", data, icov=100.0)
-        kw = dict(likelihood="gaussian", data=data, icov=100.0)
-    lin = orc.Linearized(cf, lho, x)
-    mv = lin.metric(v)
-    tol = 1e-9 if dtype == torch.float64 else 2e-4
-
-    def rel(a, b):
-        return max(float(np.max(np.abs(a[k] - b[k])) / max(np.max(np.abs(b[k])), 1e-30)) for k in ("xi", "spectrum"))
-
-    results = []
-    for sandwich, fused_dir, recur in (("2", "1", "0"), ("2", "0", "0"), ("0", "0", "0"), ("2", "1", "1")):
-        monkeypatch.setenv("NK_SANDWICH", sandwich)
-        monkeypatch.setenv("NK_CG_FUSED_DIRECTION", fused_dir)
-        monkeypatch.setenv("NK_CG_ENERGY_RECURRENCE", recur)  # 1: energy of the CG iterate by recurrence (nk_cg_update_dr)
-        model = FusedModel(shape, offset_mean=1.0, dtype=dtype, device="cuda:0", **kw)
-        assert model.sandwich == (sandwich == "2") and model.fused_direction == (fused_dir == "1")
-        xl, vl = LatentVec.from_dict(model, x), LatentVec.from_dict(model, v)
-        lp = model.linearize(xl)
-        assert rel(model.metric(lp, vl).to_dict(), mv) < tol
-        random.push_sseq_from_seed(7)
-        res, negs, _ = draw_samples(model, xl, 1, True, lambda: AbsDeltaEnergyController(0.05, iteration_limit=6))
-        random.pop_sseq()
-        kl = FusedKL(model, xl, res, negs)
-        results.append((res[0].to_dict(), kl.value, kl.apply_metric(vl).to_dict()))
-    res_o, negs_o = orc.draw_samples(cf, lho, x, 1, True, np.random.SeedSequence(7),
-                                     lambda: orc.AbsDeltaEnergyController(0.05, iteration_limit=6))
-    kl_o = orc.SampledKL(cf, lho, x, res_o, negs_o)
-    ctol = 1e-7 if dtype == torch.float64 else 5e-3  # six CG iterations amplify rounding differences
-    for r0, val, mv_kl in results:
-        assert rel(r0, res_o[0]) < ctol
-        assert abs(val - kl_o.value) < (1e-8 if dtype == torch.float64 else 1e-4) * abs(kl_o.value)
-        assert rel(mv_kl, kl_o.apply_metric(v)) < ctol
-    # the fused and the separate direction update are the same arithmetic
-    assert rel(results[0][0], results[1][0]) < (1e-12 if dtype == torch.float64 else 1e-5)
+    numpy oracle; and the same run with the fusions switched off (the body, shared with the routes of
+    tests/test_engine_routes_gpu.py: engine_route_cases.sandwich_engine_vs_oracle)."""
+    rc.sandwich_engine_vs_oracle(shape, dtype, lh, monkeypatch)
 
 
 @pytest.mark.parametrize("shape,dtype", [((64, 64, 128), torch.float64), ((64, 128, 128), torch.float32)])

@@ -555,16 +555,17 @@ def test_anisotropic_grid_scatter_eligibility_is_counted_exactly(shape):
     """the overflow bound of the fixed-point scatter (< 2^18 points per (shell, split) workgroup) is counted
     from the bin index of the grid at hand, not from a cube heuristic; the VJP bin sums of a non-cubic grid with equal
     physical box lengths agree with the host bincount."""
-    from nifty_amd import random
+    from nifty_amd import engine, random
     from nifty_amd.engine import FusedModel
 
+    assert engine.SCATTER_FIXED_POINT_MAX_POINTS == 1 << 18
     model = FusedModel(shape, offset_mean=1.0, likelihood="gaussian", icov=10.0, dtype=torch.float64, device="cuda:0")
     if model.bin_k2 is not None:
         a = np.arange(shape[0] // 2 + 1)
         p8 = model.pidx8.cpu().numpy().reshape(shape[0] // 2 + 1, -1)
         key = (p8 // 4096) * 16 + (a % 16)[:, None]
         assert model.scatter_busiest == int(np.bincount(key.ravel()).max())
-        assert model.scatter_fixed_point == (model.scatter_busiest < (1 << 18))
+        assert model.scatter_fixed_point == (model.scatter_busiest < engine.SCATTER_FIXED_POINT_MAX_POINTS)
     random.push_sseq_from_seed(2)
     try:
         x = model.draw_prior() * 0.1
