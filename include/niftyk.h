@@ -584,6 +584,15 @@ int nk_pcg64_integers(const uint64_t* state, const uint64_t* inc, int64_t n, int
 /* 1 if nk_hartley_fused_batch runs the members of this plan in shared launches (2-D plans of the register-resident
  * pipeline, nk_plan_octant_vjp != 0); 0: it falls back to one nk_hartley_fused per member (same results) */
 int nk_plan_batch_ok(const nk_plan* plan);
+/* 1 exactly when nk_hartley_fused_batch with count >= 2 runs records of the kernel classes of `fuse` in shared launches
+ * (the very function that call decides with; host only, nothing is launched): nk_plan_batch_ok(plan), both axes at
+ * least 512 points, and a batched twin for both passes --
+ *   prologue: PLAIN, MUL, or AMP / AMP_JVP with field_octant set and io32 unset;
+ *   epilogue: MUL, NONLIN, LIKELIHOOD with io32 unset, or VJP with `afield` set.
+ * 0: every other class (AFFINE, a VJP without `afield`, table or full-field amplitude prologues, io32), a smaller or
+ * a 3-D plan, the developer switch NK_EC_GENERIC, a NULL argument: the members run one after the other, each as nk_hartley_fused (same results).  Only the
+ * fields named here are read; the pointers need not be valid. */
+int nk_plan_batch_class_ok(const nk_plan* plan, const nk_fuse* fuse);
 /* nk_hartley_fused for fuse[0..count) on workspace[0..count) (each nk_plan_workspace_bytes, pairwise distinct).  All
  * members must select the same kernel classes: same prologue / epilogue, the same of {afield, dafield, field_octant,
  * io32} set or unset (NK_ERR_INVALID otherwise); pointers, scalars and the optional addend / accumulate / carry / value

@@ -148,6 +148,7 @@ SIGNATURES = {
     "nk_regrid_adjoint": (_i, [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     # batched launches: per-member arguments are host arrays of `count` device pointers (ptr_array)
     "nk_plan_batch_ok": (_i, [_vp]),
+    "nk_plan_batch_class_ok": (_i, [_vp, ctypes.POINTER(Fuse)]),
     "nk_hartley_fused_batch": (_i, [_vp, ctypes.POINTER(Fuse), _i, _i, _vp, _vp]),
     "nk_amp_forward_batch": (_i, [_i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "nk_amp_jvp_batch": (_i, [_i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),

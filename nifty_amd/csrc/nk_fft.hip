@@ -1115,6 +1115,10 @@ extern "C" int nk_plan_batch_ok(const nk_plan* P) {
   return P->hp.dtype == NK_F32 ? nk_fast_strided_ok<float>(hp.g.na, hp.pc.inner) : nk_fast_strided_ok<double>(hp.g.na, hp.pc.inner);
 }
 
+extern "C" int nk_plan_batch_class_ok(const nk_plan* P, const nk_fuse* fuse) {
+  return (fuse && nk_plan_batch_ok(P) && nk_batch_class_ok(P->hp.g, *fuse)) ? 1 : 0;
+}
+
 template <typename T>
 static int nk_run_hartley_batch(const nk_plan* P, const nk_fuse* fuse, int count, int convention, void* const* workspace,
                                 hipStream_t st) {
@@ -1201,7 +1205,7 @@ extern "C" int nk_hartley_fused_batch(const nk_plan* P, const nk_fuse* fuse, int
       return nk_set_error(NK_ERR_INVALID, "nk_hartley_fused_batch: the members select different kernel classes");
   }
   hipStream_t st = (hipStream_t)stream;
-  if (count == 1 || !nk_plan_batch_ok(P) || !nk_batch_class_ok(P->hp.g, fuse[0])) {  // one launch set per member: same results
+  if (count == 1 || !nk_plan_batch_class_ok(P, fuse)) {  // one launch set per member: same results
     for (int m = 0; m < count; ++m) {
       const int rc = P->hp.dtype == NK_F32 ? nk_run_hartley<float>(P, fuse[m], convention, workspace[m], st)
                                            : nk_run_hartley<double>(P, fuse[m], convention, workspace[m], st);

@@ -258,15 +258,23 @@ def _same(a, b):
     assert a["counters"]["metric"] == b["counters"]["metric"] and a["counters"]["value_grad"] == b["counters"]["value_grad"]
 
 
-@pytest.mark.parametrize("shape,likelihood,pairs", [((512, 512), "poisson", 4), ((1024, 512), "gaussian", 3), ((512, 512), "gaussian", 5)])
+# (4096, 512): the two-level first axis (k2_tl_b) inside a whole iteration -- no other iteration of the suite reaches a
+# twin beyond 1024 points; against the stream lanes only (a third run of 2 M points buys nothing the two do not show)
+LANES_ONLY = {(4096, 512)}
+
+
+@pytest.mark.parametrize("shape,likelihood,pairs", [((512, 512), "poisson", 4), ((1024, 512), "gaussian", 3), ((512, 512), "gaussian", 5),
+                                                    ((4096, 512), "gaussian", 2)])
 def test_mgvi_iteration_batched_equals_lanes_and_sequential(shape, likelihood, pairs, monkeypatch):
     """sampling solves (22 CG iterations: through the residual refresh at 20), KL value / gradient / metric, a Newton-CG
     minimisation: batched == four stream lanes == one chain after the other, bit for bit; 5 pairs = 10 samples also runs a
     second wave of the batch"""
-    batch = _iteration(shape, likelihood, pairs, {"NK_BATCH": "1"}, monkeypatch)
+    batch = _iteration(shape, likelihood, pairs, {"NK_BATCH": "1"}, monkeypatch)  # (asserts batched.ready(model))
     lanes = _iteration(shape, likelihood, pairs, {"NK_BATCH": "0"}, monkeypatch)
-    plain = _iteration(shape, likelihood, pairs, {"NK_BATCH": "0", "NK_LANES": "0"}, monkeypatch)
     _same(batch, lanes)
+    if shape in LANES_ONLY:
+        return
+    plain = _iteration(shape, likelihood, pairs, {"NK_BATCH": "0", "NK_LANES": "0"}, monkeypatch)
     _same(batch, plain)
 
 

@@ -67,6 +67,19 @@ def test_impulse_positions_cover_the_edges():
     assert any(p[-1] % 2 == 1 and p[0] for p in pos) and any(p[-1] % 2 == 0 and p[-1] and p[0] for p in pos)
 
 
+@pytest.mark.parametrize("shape", [s for s in ALL_SHAPES if np.prod(s) <= 64 * 128] + [(7, 9), (5, 6, 7)])
+def test_bin_index_from_integer_k2_equals_the_power_space(shape):
+    """real_pindex ranks the integer k^2 (pindex_from_k2) instead of building a PowerSpace: the same index and bin count
+    on every shape of the route table up to (64, 128) and on two grids with odd axes (no Nyquist plane on those axes)."""
+    want, nb_want = tc.pindex_powerspace(shape)
+    got, nb = tc.pindex_from_k2(shape)
+    assert nb == nb_want and got.dtype == want.dtype == np.int32 and got.shape == want.shape == tuple(shape)
+    assert np.array_equal(got, want)
+    if all(n % 2 == 0 for n in shape):  # real_pindex asserts a Nyquist-only bin
+        cached, nb_cached = tc.real_pindex(shape)
+        assert nb_cached == nb and np.array_equal(cached, want) and not cached.flags.writeable
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("shape", [(30,), (10, 12), (64, 128), (6, 64, 96)])
 def test_comparators_reject_wrong_transforms(shape, dtype):

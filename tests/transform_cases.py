@@ -262,26 +262,47 @@ def impulse_positions(shape):
     return sorted(set(pos))
 
 
-@functools.lru_cache(maxsize=8)
-def real_pindex(shape):
-    """PowerSpace.pindex of the grid as int32 and the number of bins, with the properties the VJP's mirror merging and the
-    tests rely on checked: symmetric under every single-axis flip, a single-member bin, a Nyquist-only bin."""
+def pindex_powerspace(shape):
+    """(PowerSpace.pindex of the default-distance grid as int32, number of bins)"""
     import nifty_amd as ift
 
     ps = ift.PowerSpace(ift.RGSpace(shape).get_default_codomain())
-    pidx = np.ascontiguousarray(np.array(ps.pindex).astype(np.int32))
+    return np.ascontiguousarray(np.array(ps.pindex).astype(np.int32)), int(ps.shape[0])
+
+
+def pindex_from_k2(shape):
+    """The same index without a PowerSpace: the harmonic partner of a default-distance grid has unit distances on every
+    axis, so |k|^2 = sum_d min(i_d, n_d - i_d)^2 is an integer, distinct integers have distinct square roots, and the
+    natural binning (one bin per distinct |k|, in ascending order) is the rank of k^2 among its distinct values.
+    tests/test_transform_cases.py holds it against pindex_powerspace."""
+    k2 = np.zeros((), dtype=np.int64)
+    for n in shape:
+        ax = np.arange(n, dtype=np.int64)
+        k2 = np.add.outer(k2, np.minimum(ax, n - ax) ** 2)
+    uniq, inv = np.unique(k2.ravel(), return_inverse=True)
+    return np.ascontiguousarray(inv.reshape(shape).astype(np.int32)), int(uniq.size)
+
+
+# the index of one shape is shared by every case on it; tests/test_batched_transforms_gpu.py alone walks seven shapes
+@functools.lru_cache(maxsize=32)
+def real_pindex(shape):
+    """PowerSpace.pindex of the grid as int32 and the number of bins (computed from the integer k^2: pindex_from_k2), with
+    the properties the VJP's mirror merging and the tests rely on checked: symmetric under every single-axis flip, a
+    single-member bin, a Nyquist-only bin."""
+    pidx, nb = pindex_from_k2(tuple(shape))
     pidx.setflags(write=False)  # cached: shared by every case of the shape
-    nb = int(ps.shape[0])
     idx = np.indices(shape)
     for d in range(len(shape)):
         flip = tuple((-idx[e]) % shape[e] if e == d else idx[e] for e in range(len(shape)))
         assert np.array_equal(pidx, pidx[flip])
     counts = np.bincount(pidx.ravel(), minlength=nb)
-    assert counts[pidx[tuple([0] * len(shape))]] == 1
+    assert counts.min() > 0 and counts[pidx[tuple([0] * len(shape))]] == 1
     on_nyq = np.zeros(shape, dtype=bool)
     for d, n in enumerate(shape):
         on_nyq |= idx[d] == n // 2
-    assert any(on_nyq[pidx == b].all() for b in range(nb) if counts[b])
+    # a bin all of whose members lie on a Nyquist plane: as many members on the planes as members (one pass over the
+    # grid instead of one per bin)
+    assert np.any(np.bincount(pidx.ravel(), weights=on_nyq.ravel(), minlength=nb) == counts)
     return pidx, nb
 
 
@@ -401,8 +422,26 @@ SANDWICH = [((64, 128), None), ((64, 64, 128), None), ((64, 64, 1024), None), ((
             ((64, 1024, 128), np.float32)]  # (shape, the only dtype it runs in or None = both)
 
 
+# nk_hartley_fused_batch (tests/test_batched_transforms_gpu.py): the batched twins of the first and the final pass exist for
+# axis lengths 512 .. 4096 and need both axes >= 512 -- the smallest grid of every twin instantiation, same columns as ROUTES
+SF1, SF2 = (2, 1, -1, 1), (2, 1, -1, 2)
+BATCH_SHAPES = [
+    ((512, 512), SF1, SF1),
+    ((1024, 512), SF1, SF1), ((512, 1024), SF1, SF1),
+    ((2048, 512), SF1, SF1), ((512, 2048), SF1, SF1),  # final pass of 2048 fp64 points: the single-pair VJP build
+    ((4096, 512), SF2, SF1),  # two-level first axis in fp64 only
+    ((512, 4096), SF1, SF1),  # final pass of 4096 points: the single-pair VJP build in both dtypes
+]
+
+
+def final_single_pair_vjp(shape, dtype):
+    """2-D VJP final pass on single line pairs instead of the couple tile (nk_final_single_2d, nk_fft2.h): lines whose
+    couple tile exceeds 60 KiB of LDS -- 2048 and 4096 points in fp64, 4096 in fp32"""
+    return len(shape) == 2 and shape[-1] >= (4096 if np.dtype(dtype) == np.float32 else 2048)
+
+
 def route_of(shape, dtype):
-    for s, r64, r32 in ROUTES:
+    for s, r64, r32 in ROUTES + BATCH_SHAPES:
         if s == tuple(shape):
             return r32 if np.dtype(dtype) == np.float32 else r64
     raise KeyError(shape)
@@ -581,7 +620,12 @@ class FusedCase:
         self._x = x
         nd, n = len(self.shape), float(self.n)
         if self.sandwich is None:
-            t = LD(self.scale) * hartley_ld(x, nd, sign)
+            # both conventions are Re F +- Im F of ONE long-double spectrum; a case asked for both (the batched tests)
+            # transforms once.  The operands of a case are fixed once a reference has been taken.
+            if getattr(self, "_spectrum", None) is None:
+                self._spectrum = scipy.fft.fftn(x)
+                assert self._spectrum.dtype == np.complex256
+            t = LD(self.scale) * (self._spectrum.real + sign * self._spectrum.imag)
             return t, transform_abs_bound(x, x_abs, self.shape, self.dtype, abs(self.scale), rel, self.pro_ops)
         sf, ms, _ = self.sandwich
         s1 = LD(sf) * hartley_ld(x, nd, sign)
